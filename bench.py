@@ -21,8 +21,12 @@ QuantAct ranges; in the `e2e` leg a per-batch all_gather of the detections [B,10
 configs[3] (CoDeNet2x, 32 images per GPU, global 256 at 8 GPUs), --config cfg2 = configs[1] (256x256 fp32,
 batch 32).
 
-Rank 0 prints ONE JSON line with
+A plain run sets up, warms up (--warmup steps, then min(--steps, SETTLE_STEPS) untimed steps), times exactly --steps
+steps (one region), writes the last step's outputs when --dump-outputs DIR is given and prints ONE JSON line on rank 0
+with the headline (metric, value, unit, ms_per_step, ...).  --full adds everything else the benchmark measures, as extra
+keys of the same line (and 15 regions by default):
   roofline          dominant kernel family (the gather), live HIP-event timing on its launch stream
+  with_unpack, frozen_int8, configs   the hand-over copy, the frozen byte-code schedule, the other BASELINE configs
   cpu_baseline      the CPU oracle timed on a bounded sample of the same hot-path workload (N = 1 only)
   e2e               whole network (native backbone + stages + heads) + native ctdet_decode as one HIP graph
   cpu_baseline_e2e  whole model + decode on the CPU oracle path, batch 1 and 8, all cores and 1 thread
@@ -48,15 +52,30 @@ PRESETS = {
     "cfg4": dict(res=512, batch=32, w2=True, fp32=False),     # BASELINE configs[3]: 256 images over 8 GPUs
 }
 
+# --dump-outputs: an output of more elements is written as this many of them (16 MB of float32 per array; the
+# default step's output has 16.8 M elements)
+DUMP_SAMPLE = 1 << 22
+
+# plain run: at most this many untimed steps between the warm-up and the one timed region (50 ms of the default step)
+SETTLE_STEPS = 200
+
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--regions", type=int, default=15,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beyond the headline: roofline and per-kernel times, "
+                         "with_unpack, frozen_int8, e2e, configs, the CPU baselines (each --no-* option below skips "
+                         "one of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed step returned in its last step as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of an output larger than %d elements)" % DUMP_SAMPLE)
+    ap.add_argument("--regions", type=int, default=None,
                     help="the timed K-step region (barrier + synchronize on both sides) is run this many times "
-                         "back to back; the headline ms_per_step is the MEDIAN region, min / max are reported")
+                         "back to back; the headline ms_per_step is the MEDIAN region, min / max are reported "
+                         "(default 1, so that --steps is the number of timed steps; 15 with --full)")
     ap.add_argument("--config", choices=sorted(PRESETS), default=None,
                     help="preset of --res/--batch/--w2/--fp32 (default: cfg3 values)")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step")
@@ -90,6 +109,8 @@ def parse(argv=None):
     for k in ("batch", "res", "w2", "fp32"):
         if getattr(a, k) is None:
             setattr(a, k, base[k])
+    if a.regions is None:
+        a.regions = 15 if a.full else 1
     if a.backend == "gloo" and not a.plumbing_only:
         ap.error("--backend gloo runs no kernels: use it with --plumbing-only")
     return a
@@ -178,7 +199,7 @@ def live_pmc_traffic(args):
             return None                              # already under a profiler: no nested profiling
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import pmc_steady
-        base = [sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "2", "--no-graph",
+        base = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "3", "--warmup", "2", "--no-graph",
                 "--no-cpu-baseline", "--no-e2e", "--no-config-legs", "--no-live-pmc", "--regions", "1", "--batch", str(args.batch),
                 "--res", str(args.res)] + (["--w2"] if args.w2 else []) + (["--fp32"] if args.fp32 else []) + \
                (["--frozen"] if args.frozen else [])
@@ -615,6 +636,22 @@ def plumbing_only(args, world, rank):
 
 # ---- the measured run ----------------------------------------------------------------------------------------
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (float64 kept).  An array of more than DUMP_SAMPLE
+    elements is written flattened as DUMP_SAMPLE of its elements in index order, picked by a fixed seed: the same
+    positions for the same shape in every run, so that two builds compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -632,7 +669,7 @@ def main():
     # roofline.traffic measured in THIS run (N = 1): two short profiled child runs, started before this process
     # touches the GPU
     live_traffic = None
-    if world == 1 and rank == 0 and not args.no_live_pmc and not args.no_graph:
+    if args.full and world == 1 and rank == 0 and not args.no_live_pmc and not args.no_graph:
         live_traffic = live_pmc_traffic(args)
 
     import torch
@@ -657,7 +694,7 @@ def main():
     # rank 0 owns the weights; the other ranks start from different values and receive them
     net = pipeline.build_hot_path(w2=args.w2, quantized=quantized, seed=317 if rank == 0 else 1000 + rank)
     net_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import copy
         net_cpu = copy.deepcopy(net)
     net = net.to(dev)
@@ -703,12 +740,19 @@ def main():
         step = eager_step
     for _ in range(args.warmup):
         step()
+    if not args.full:
+        # the one timed region of a plain run must not start while the clocks still ramp up: right after a few ms of
+        # warm-up a region reads ~0.4 % slower than the steady state the median of --full's regions gives.  One untimed
+        # region of the same length first (at most SETTLE_STEPS); a fixed count, so that the last step's outputs are the
+        # same in every run
+        for _ in range(min(args.steps, SETTLE_STEPS)):
+            step()
     barrier()
     # ---- timed regions: each is exactly K steps between barrier + synchronize; R of them back to back,
     #      MAX over ranks per region, headline = the median region (one region = ms_per_step * steps) ------
     names = {"scale", "dw", "pointwise", "quantact"}
     region_s = []
-    with ops.KernelTimer(names if fused is None else set()) as kt:
+    with ops.KernelTimer(names if (fused is None and args.full) else set()) as kt:
         for _ in range(max(1, args.regions)):
             barrier()
             t0 = time.perf_counter()
@@ -725,10 +769,19 @@ def main():
     assert out.dtype == torch.int8 or torch.isfinite(out).all()
     if frozen_main:
         assert not frz.overflowed(), "a code left its frozen 8-bit grid: this batch needs the fp32 schedule"
+    if args.dump_outputs and rank == 0:
+        # what the timed step hands its caller, before any later leg overwrites it: the last stage's output and, on the
+        # fused W4A8 schedules, the range of the QuantAct whose state travels with it (the heads quantise with it)
+        arrays = {"output": out}
+        if quantized and fused is not None:
+            from codenet_amd.portable_quantizer.quant_modules import QuantAct
+            act = [m for m in net.deconv_layers.modules() if isinstance(m, QuantAct)][-1]
+            arrays["output_range"] = torch.cat([act.x_min.reshape(-1), act.x_max.reshape(-1)])
+        dump_outputs(args.dump_outputs, arrays)
 
     # ---- the same step + the NCHW / up-sampled copy for a PyTorch consumer (reported separately) ---
     with_unpack_ms = None
-    if fused is not None:
+    if args.full and fused is not None:
         if use_graph:
             step_u = frz.capture(x, codes_only=False) if frozen_main else fused.capture(x, unpack=True)
         else:
@@ -745,18 +798,18 @@ def main():
     # ---- per-kernel durations: HIP events on the launch stream (fused path: the library's own
     #      event pairs around every kernel, K eager steps right after the timed region) ------------
     durs = {}
-    if fused is not None and rank == 0:
+    if args.full and fused is not None and rank == 0:
         # `eager_step` is the TIMED step: until round 3 these steps also ran unpack_kernel (320 MB through the caches
         # between two steps), which made the kernels behind it 10-40 % slower than inside the timed region
         kernel_event_durations(eager_step, args.steps, lambda nm: nm != "unpack", durs)
         kernel_event_durations(eager_step_unpack, args.steps, lambda nm: nm == "unpack", durs)   # (`with_unpack`)
-    elif rank == 0:
+    elif args.full and rank == 0:
         durs = kt.durations_ms()
 
     # ---- "reported both running (reference-faithful) and frozen": the frozen byte-code schedule on the
     #      ranges the timed running steps left behind (same weights, same input), K graph replays ---------------
     frozen_leg = None
-    if frz is not None and not frozen_main and use_graph:
+    if args.full and frz is not None and not frozen_main and use_graph:
         stepf = frz.capture(x)
         for _ in range(5):
             stepf()
@@ -821,12 +874,13 @@ def main():
 
     # ---- whole network + native decode as one HIP graph (every rank; per-batch detections all_gather) ---
     e2e = None
-    if not args.no_e2e and args.path == "fused":
+    if args.full and not args.no_e2e and args.path == "fused":
         e2e = e2e_leg(args, dev, rank, world, local_rank, dt / args.steps * 1e3)
 
     # ---- the other BASELINE configs, timed by the same run (N = 1, default workload only): VERDICT r4 "next" #1a ----
     configs = None
-    if rank == 0 and world == 1 and args.config is None and not args.no_config_legs and args.path == "fused" \
+    if args.full and rank == 0 and world == 1 and args.config is None and not args.no_config_legs \
+            and args.path == "fused" \
             and (args.res, args.batch, args.w2, args.fp32, args.frozen) == (512, 64, False, False, False):
         configs = {}
         for key, fn in (("cfg2", lambda: hot_path_config_leg("cfg2", dev, args.steps, args.warmup)),
@@ -838,7 +892,7 @@ def main():
                 configs[key] = {"error": "%s: %s" % (type(exc).__name__, exc)}
             torch.cuda.empty_cache()
 
-    if rank == 0:
+    if args.full and rank == 0:
         per_kernel = {}
         for (name, tag), v in durs.items():
             per_kernel.setdefault(name, 0.0)
@@ -917,6 +971,7 @@ def main():
                                 for k in ("dw", "pointwise", "scale") if per_kernel.get(k)}
         roof["launches_per_step"] = sum(1 for (nm, _t) in durs if nm == dominant)
         roof["ms_per_step_in_kernel"] = per_kernel[dominant]
+    if rank == 0:
         ms_step = dt / args.steps * 1e3
         res = {
             "metric": "images/sec CoDeNet%s %dx%d ctdet inference (deform hot path: deconv_layers; whole network in `e2e`)"
@@ -933,7 +988,6 @@ def main():
                         "ms_per_step_max": region_s[-1] / args.steps * 1e3,
                         "note": "every region = exactly `steps` steps between barrier + synchronize, MAX over "
                                 "ranks; value / ms_per_step are the median region"},
-            "gpu_clock": gpu_clock_state(local_rank),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -955,25 +1009,30 @@ def main():
                 "parallelism": "dp%d (independent image shards, start-up RCCL broadcast of %d bytes, per-batch "
                                "all_gather of detections in the e2e leg)" % (world, bcast_bytes),
             },
-            "roofline": roof,
-            "with_unpack": (None if with_unpack_ms is None else
-                            {"ms_per_step": with_unpack_ms, "images_per_s": world * args.batch / with_unpack_ms * 1e3,
-                             "note": "step + unpack_kernel (fake-quant + nearest x2 + NCHW copy for a PyTorch "
-                                     "consumer; the native heads do not need it)"}),
-            "kernel_ms_per_step": per_kernel,
-            "kernel_ms_per_launch": per_launch,
-            "frozen_int8": frozen_leg,
-            "e2e": e2e,
-            "configs": configs,
         }
-        if net_cpu is not None:
-            res["cpu_baseline"] = cpu_baseline(args, net_cpu)
-            res["cpu_baseline_e2e"] = cpu_baseline_e2e(args) if e2e is not None else None
-            if e2e is not None and res["cpu_baseline_e2e"]:
-                res["e2e"]["vs_cpu_baseline_e2e"] = e2e["images_per_s"] / res["cpu_baseline_e2e"]["value"]
-        else:
-            res["cpu_baseline"] = None
-            res["cpu_baseline_e2e"] = None
+        if args.full:
+            res.update({
+                "gpu_clock": gpu_clock_state(local_rank),
+                "roofline": roof,
+                "with_unpack": (None if with_unpack_ms is None else
+                                {"ms_per_step": with_unpack_ms,
+                                 "images_per_s": world * args.batch / with_unpack_ms * 1e3,
+                                 "note": "step + unpack_kernel (fake-quant + nearest x2 + NCHW copy for a PyTorch "
+                                         "consumer; the native heads do not need it)"}),
+                "kernel_ms_per_step": per_kernel,
+                "kernel_ms_per_launch": per_launch,
+                "frozen_int8": frozen_leg,
+                "e2e": e2e,
+                "configs": configs,
+            })
+            if net_cpu is not None:
+                res["cpu_baseline"] = cpu_baseline(args, net_cpu)
+                res["cpu_baseline_e2e"] = cpu_baseline_e2e(args) if e2e is not None else None
+                if e2e is not None and res["cpu_baseline_e2e"]:
+                    res["e2e"]["vs_cpu_baseline_e2e"] = e2e["images_per_s"] / res["cpu_baseline_e2e"]["value"]
+            else:
+                res["cpu_baseline"] = None
+                res["cpu_baseline_e2e"] = None
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

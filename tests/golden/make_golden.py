@@ -29,6 +29,8 @@ Fixtures
                     and `linear_errors`: the exception every QuantLinear configuration raises in the reference.
   deform_raw.npz    oracle-only regression vectors for the generic op (fwd + all grads, plain
                     and modulated); the reference cannot produce these (CUDA-only).
+  reference_names.npz   names only: the state_dict keys and shapes of the reference's PoseShuffleNetV2(heads, 64) in
+                    fp32 and after its own quantiser, and the class list of its portable_quantizer/quant_modules.py.
 
 Usage:  python tests/golden/make_golden.py
 """
@@ -824,6 +826,29 @@ def make_post_process():
     return out
 
 
+def make_reference_names():
+    """The checkpoint layout the package's network and quantiser must reproduce (tests/test_host_api.py,
+    tests/test_quant_surface.py): keys + shapes of the reference network in fp32 and after the reference's quantiser
+    (the arguments base_detector.py passes), and the class names of the reference's quantiser module."""
+    import re
+    import models.networks.shufflenetv2_dcn as ref_net
+    from portable_quantizer import quantize_shufflenetv2_dcn as ref_quantize
+    torch.manual_seed(0)
+    net = ref_net.PoseShuffleNetV2({"hm": 20, "wh": 2, "reg": 2}, 64)
+    out = {}
+
+    def names(tag):
+        items = sorted(net.state_dict().items())
+        out[tag + "_keys"] = np.array([k for k, _ in items])
+        out[tag + "_shapes"] = np.array(["x".join(str(n) for n in v.shape) for _, v in items])
+    names("fp")
+    ref_quantize(net, 4, None, 8, "symmetric", "asymmetric", True, False, False, False)
+    names("q")
+    src = open(os.path.join(REF, "portable_quantizer", "quant_modules.py")).read()
+    out["quant_modules_classes"] = np.array(re.findall(r"^class (\w+)", src, re.M))
+    return out
+
+
 def main():
     assert os.path.isdir(REF), "needs the reference checkout at /root/reference"
     torch.manual_seed(317)
@@ -846,6 +871,7 @@ def main():
         "quant_extra": lambda: make_quant_extra(ref_mod, ref_qm),
         "voc_eval_ref": make_voc_eval,
         "post_process_ref": make_post_process,
+        "reference_names": make_reference_names,
     }
     only = sys.argv[1:] or list(makers)           # `make_golden.py stage_w4a8_grads` regenerates one fixture
     for name in only:

@@ -15,7 +15,6 @@ import torch.nn as nn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
-REF = "/root/reference"
 
 
 def load(name):
@@ -265,58 +264,27 @@ def test_broadcast_style_copy_bumps_versions_and_bn_affine_cache_follows():
     assert torch.allclose(eh1, -es1)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 def test_drop_in_under_reference_network():
-    """The reference's own PoseShuffleNetV2 (imported from /root/reference, not copied) builds on
-    OUR operator module when it is installed at the reference's import path, and our quantiser
-    rewrites it to the same module tree / checkpoint keys as the reference's quantiser."""
-    code = r'''
-import sys, types, os
-ROOT, REF = sys.argv[1], sys.argv[2]
-sys.path.insert(0, ROOT)
-for name in ["pytorchcv", "pytorchcv.model_provider", "pytorchcv.models", "pytorchcv.models.shufflenetv2",
-             "pytorchcv.models.common", "thop", "_ext", "_ext.dcn", "_ext.dcn.dcn_deform_conv_cuda"]:
-    sys.modules.setdefault(name, types.ModuleType(name))
-sys.modules["pytorchcv.model_provider"].get_model = lambda *a, **k: None
-sys.modules["pytorchcv.models.shufflenetv2"].ShuffleUnit = type("ShuffleUnit", (), {})
-sys.modules["pytorchcv.models.common"].ChannelShuffle = type("ChannelShuffle", (), {})
-sys.modules["thop"].profile = lambda *a, **k: (0, 0)
-sys.path.insert(0, os.path.join(REF, "lib")); sys.path.insert(0, REF)
-import torch
-mode = sys.argv[3]
-if mode == "ours":
-    import codenet_amd.modules.dcn_deform_conv as ours
-    import models, models.external                      # reference packages (namespace)
-    pkg = types.ModuleType("models.external.modules"); pkg.__path__ = []
-    pkg.dcn_deform_conv = ours
-    sys.modules["models.external.modules"] = pkg
-    sys.modules["models.external.modules.dcn_deform_conv"] = ours
+    """The package's PoseShuffleNetV2 (codenet_amd.harness, built on OUR operator module) has the module tree /
+    checkpoint keys of the reference's PoseShuffleNetV2, and our quantiser rewrites it to the keys the reference's
+    quantiser gives the reference network -- both recorded from the reference itself in
+    tests/golden/reference_names.npz (make_golden.py)."""
+    from codenet_amd import harness
     from codenet_amd.portable_quantizer import quantize_shufflenetv2_dcn
-else:
-    from portable_quantizer import quantize_shufflenetv2_dcn
-from models.networks.shufflenetv2_dcn import PoseShuffleNetV2
-torch.manual_seed(0)
-net = PoseShuffleNetV2({"hm": 20, "wh": 2, "reg": 2}, 64)
-k_fp = sorted((k, tuple(v.shape)) for k, v in net.state_dict().items())
-cls = type(net.deconv_layers[0]).__module__
-quantize_shufflenetv2_dcn(net, 4, None, 8, "symmetric", "asymmetric", True, False, False, False)
-k_q = sorted((k, tuple(v.shape)) for k, v in net.state_dict().items())
-import json
-print(json.dumps({"cls": cls, "fp": k_fp, "q": k_q}))
-'''
-    import json
-    import subprocess
-    outs = {}
-    for mode in ("ours", "ref"):
-        r = subprocess.run([sys.executable, "-c", code, ROOT, REF, mode], capture_output=True,
-                           text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        outs[mode] = json.loads(r.stdout.strip().splitlines()[-1])
-    assert outs["ours"]["cls"] == "codenet_amd.modules.dcn_deform_conv"
-    assert outs["ours"]["fp"] == outs["ref"]["fp"]
-    assert outs["ours"]["q"] == outs["ref"]["q"]
-    assert len(outs["ours"]["q"]) > 300
+    z = np.load(os.path.join(G, "reference_names.npz"))
+
+    def ref(tag):
+        return list(zip(z[tag + "_keys"].tolist(), z[tag + "_shapes"].tolist()))
+
+    def ours(net):
+        return [(k, "x".join(str(n) for n in v.shape)) for k, v in sorted(net.state_dict().items())]
+    torch.manual_seed(0)
+    net = harness.PoseShuffleNetV2({"hm": 20, "wh": 2, "reg": 2}, 64)
+    assert type(net.deconv_layers[0]).__module__ == "codenet_amd.modules.dcn_deform_conv"
+    assert ours(net) == ref("fp")
+    quantize_shufflenetv2_dcn(net, 4, None, 8, "symmetric", "asymmetric", True, False, False, False)
+    assert ours(net) == ref("q")
+    assert len(ref("q")) > 300
 
 
 def test_argument_validation_of_round2_entry_points_without_gpu():

@@ -8,7 +8,7 @@ R=${1:-r06}
 OUT="gpurun_out/$R"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-P="--steps 3 --warmup 2 --no-graph --no-cpu-baseline --no-e2e --no-config-legs"
+P="--full --steps 3 --warmup 2 --no-graph --no-cpu-baseline --no-e2e --no-config-legs"
 run() {   # name, marker, per-iter, command...
   local name=$1 marker=$2 per=$3; shift 3
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pv_${name}_f" -- "$@" > "$OUT/pv_${name}.log" 2>&1

@@ -7,7 +7,7 @@ R=${1:-r06}
 OUT="gpurun_out/$R"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python3 bench.py"
+B="python3 bench.py --full"
 $B > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
 $B --frozen --no-cpu-baseline > "$OUT/bench_frozen.json" 2>/dev/null
 $B --fp32 --no-cpu-baseline > "$OUT/bench_fp32.json" 2>/dev/null
