@@ -134,8 +134,6 @@ class CodenetStageFunction(Function):
                                         and not getattr(post_act, "global_range", False)) else None)
             y, yp = ops.codenet_pointwise(d_q, w_pw, b_pw, want_range=True, d_state=d_snap, int8_weights=pw_int8, keep=keep,
                                           update_act=upd)
-            if keep.get("range_committed"):
-                post_act._range_committed = True      # (ReluQuant / ReluQuantUpsample behind the stage: apply only)
         else:
             y = ops.codenet_pointwise(d_q, w_pw, b_pw, d_state=d_snap, int8_weights=pw_int8, keep=keep) if have_pw else d_q
         ctx.pw_fwd_ws = keep.get("fwd_ws")      # (the int8 forward's weight scales: the data gradient reads them)
@@ -144,7 +142,7 @@ class CodenetStageFunction(Function):
         ctx.save_for_backward(x, s_c, s, w_scale, w_dw, d_q if have_pw else None, w_pw, d_snap)
         if want_range:
             if yp is None:
-                yp = y.new_zeros(0, 2)
+                yp = y.new_zeros(0, 0) if keep.get("range_committed") else y.new_zeros(0, 2)
             ctx.mark_non_differentiable(yp)
             return y, yp
         return y
@@ -232,10 +230,17 @@ def _native_quantact(act, t):
 def codenet_stage(x, w_scale, b_scale, w_dw, w_pw, b_pw, lo, hi, act_s=None, act_d=None, want_range=False, x_up=False,
                   pw_int8=False):
     """want_range: returns (y, partials) -- the per-workgroup {min, max} pairs of y ([n, 2], empty without a pointwise
-    conv) for a QuantAct behind the stage (ReluQuantUpsample).  x_up: see CodenetStageFunction.forward.  pw_int8: w_pw is
-    a per-channel symmetric <= 4-bit fake-quantised weight (the forward conv_channel may sum integer codes)."""
+    conv) for a QuantAct behind the stage (ReluQuantUpsample), or, when want_range IS that QuantAct and the pointwise
+    kernel already updated it, a [0, 0] tensor (range_committed).  x_up: see CodenetStageFunction.forward.  pw_int8: w_pw
+    is a per-channel symmetric <= 4-bit fake-quantised weight (the forward conv_channel may sum integer codes)."""
     return CodenetStageFunction.apply(x, w_scale, b_scale, w_dw, w_pw, b_pw, lo, hi, act_s, act_d, want_range, x_up,
                                       pw_int8)
+
+
+def range_committed(partials):
+    """True when a stage's partials output says that its pointwise kernel's last workgroup already updated the range of
+    the QuantAct behind it (round 6): the block behind the stage applies that QuantAct only."""
+    return partials is not None and partials.dim() == 2 and partials.shape[1] == 0
 
 
 class QuantActSTE(Function):
@@ -489,14 +494,13 @@ class ReluQuantUpsample(Function):
     QuantAct).  Same values as the three modules (tests/test_train_step.py)."""
 
     @staticmethod
-    def forward(ctx, y, act, partials=None):
+    def forward(ctx, y, act, partials=None, committed=False):
         ops._gpu_f32(y)
         y = y.contiguous()
         Nb, C, H, W = y.shape
         out = torch.empty(Nb, C, 2 * H, 2 * W, device=y.device)
-        if getattr(act, "_range_committed", False):
+        if committed:
             # round 6: the stage's pointwise kernel has already updated this QuantAct (its last workgroup): apply only
-            act._range_committed = False
             rc = N_.lib().cdn_quantact_relu_apply(_p(y), _p(out), Nb * C, H, W, 1, _p(act._device_state(y.device)),
                                                   ops._stream(y))
             N_.check(rc, "cdn_quantact_relu_apply")
@@ -524,7 +528,7 @@ class ReluQuantUpsample(Function):
         gy = torch.empty_like(y)
         rc = N_.lib().cdn_up2_relu_backward(_p(g), _p(y), _p(gy), Nb * C, H, W, ops._stream(y))
         N_.check(rc, "cdn_up2_relu_backward")
-        return gy, None, None
+        return gy, None, None, None
 
 
 class ReluQuant(Function):
@@ -534,12 +538,11 @@ class ReluQuant(Function):
     part of the next stage's gather backward)."""
 
     @staticmethod
-    def forward(ctx, y, act, partials=None):
+    def forward(ctx, y, act, partials=None, committed=False):
         ops._gpu_f32(y)
         y = y.contiguous()
         out = torch.empty_like(y)
-        if getattr(act, "_range_committed", False):      # (see ReluQuantUpsample.forward)
-            act._range_committed = False
+        if committed:      # (see ReluQuantUpsample.forward)
             Nb, C, H, W = y.shape
             rc = N_.lib().cdn_quantact_relu_apply(_p(y), _p(out), Nb * C, H, W, 0, _p(act._device_state(y.device)),
                                                   ops._stream(y))
@@ -563,7 +566,7 @@ class ReluQuant(Function):
         gy = torch.empty_like(y)
         rc = N_.lib().cdn_relu_backward(_p(g), _p(y), _p(gy), y.numel(), ops._stream(y))
         N_.check(rc, "cdn_relu_backward")
-        return gy, None, None
+        return gy, None, None, None
 
 
 # A/B switch (tools/train_step_bench.py --no-stored-res): stages 1-2 of the QAT step on the stored tensors (True) or on
@@ -605,6 +608,7 @@ def forward_stage_blocks(seq, x):
         pw = (pre[i // 3] if pre is not None else (None, None)) + (pre_pw[i // 3] if pre_pw is not None else (None, None))
         y = mods[i](x, want_range=mods[i + 1][1], x_up=x_up, pre_w=pw)      # (the QuantAct behind the stage: see forward)
         y, part = y if isinstance(y, tuple) else (y, None)
+        committed = range_committed(part)
         nxt = mods[i + 3] if i + 3 < len(mods) else None
         # the next stage reads its input through the up-sampling (stored tensor, never materialised) where its gather
         # kernels support the shape
@@ -612,9 +616,9 @@ def forward_stage_blocks(seq, x):
         x_up = bool(STORED_RES_STAGES and nxt is not None and nxt._train_path_ok(y) and not nxt._fast_path_ok(y)
                     and lib.cdn_codenet_dw_up2_supported(y.shape[0], y.shape[1], 2 * y.shape[2], 2 * y.shape[3]))
         if x_up:
-            x = ReluQuant.apply(y, mods[i + 1][1], part)
+            x = ReluQuant.apply(y, mods[i + 1][1], part, committed)
         else:
-            x = ReluQuantUpsample.apply(y, mods[i + 1][1], part)
+            x = ReluQuantUpsample.apply(y, mods[i + 1][1], part, committed)
     return x
 
 

@@ -117,139 +117,119 @@ class PoseShuffleNetV2(nn.Module):
         self._frozen_codes = bool(frozen_codes)
         self._frozen_backbone = bool(frozen_backbone)
         self._fpath = self._fheads = self._fbackbone = self._ffrozen = self._fzbackbone = self._fzheads = None
-        # the QuantActs whose settings decide _fused_ok(): collected once (the module tree is fixed after
-        # quantize_shufflenetv2_dcn), so a forward reads 5 attributes of ~70 modules instead of walking the tree
+        # the QuantActs whose settings key _plan(): collected once (the module tree is fixed after
+        # quantize_shufflenetv2_dcn), so a forward reads 6 attributes of ~70 modules instead of walking the tree
         self.__dict__["_fused_acts"] = [a for a in self.modules() if isinstance(a, QuantAct)]
-        self.__dict__["_fused_ok_cache"] = {}
-        self.__dict__.pop("_stage_acts", None)           # re-collected after a re-quantisation
-        self.__dict__["_fzbackbone_tried"] = None
+        self.__dict__["_plans"] = {}
         return self
 
-    def _stage_acts_frozen(self):
-        from .portable_quantizer.quant_modules import QuantAct
-        acts = self.__dict__.get("_stage_acts")
-        if acts is None:
-            acts = self.__dict__["_stage_acts"] = [a for a in self.deconv_layers.modules() if isinstance(a, QuantAct)]
-        return bool(acts) and not any(a.running_stat for a in acts)
+    def byte_backbone(self):
+        """The byte-code backbone (pipeline.FrozenBackbone) once a call on the serving schedule has built it, else None."""
+        return getattr(self, "_fzbackbone", None)
+
+    def overflowed_acts(self):
+        """The QuantActs whose byte codes saturated since the last call (synchronises; resets the flags): every launch of
+        the byte-code stages, heads and backbone names the QuantAct(s) it writes codes of (pipeline.OverflowFlags)."""
+        out = []
+        for f in (getattr(self, "_ffrozen", None), getattr(self, "_fzbackbone", None)):
+            if f is not None and f._bufs is not None:
+                out += [a for a in f._bufs["overflow"].acts() if all(a is not b for b in out)]
+        return out
 
     def frozen_overflowed(self):
-        """True when a code of the byte-code stage schedule saturated since the last call (synchronises, resets)."""
-        hit = False
-        for f in (getattr(self, "_ffrozen", None), getattr(self, "_fzbackbone", None)):
-            if f is not None and f.overflowed():
-                hit = True
-        return hit
+        """True when a code of the byte-code schedule saturated since the last call (synchronises, resets)."""
+        return bool(self.overflowed_acts())
 
-    def _fused_ok(self, x):
-        """The fused schedules implement the reference's default QuantAct settings (stored planes beyond the
-        LDS-resident gather -- inputs above ~1100 px -- are gathered from global memory); anything else
-        (--act-percentile in backbone / heads, symmetric activations) keeps the module-by-module path -- decided
-        BEFORE any kernel runs, so no QuantAct state is half-updated.  Cached per (input shape, QuantAct
-        configuration)."""
+    def _plan(self, x):
+        """The schedule of a call without autograd on the GPU tensor `x`: (schedule, byte_backbone, byte_heads) with
+        schedule "fused" (the whole network on the fp32 fused schedules), "bytes" (the deform stages on byte codes; the
+        backbone and the heads on them too where byte_backbone / byte_heads), "stages" (the deform stages alone on the
+        fused schedule, the rest module by module) or "module".  The fused schedules implement the reference's default
+        QuantAct settings (stored planes beyond the LDS-resident gather -- inputs above ~1100 px -- are gathered from
+        global memory); anything else (--act-percentile in backbone / heads, symmetric activations) keeps the module
+        path around the deform stages.  Decided BEFORE any kernel runs, so no QuantAct state is half-updated, and per
+        (input shape, QuantAct configuration), not once: a backbone frozen after the stages is picked up.  Builds the
+        schedule objects it picks on first use."""
         from . import pipeline
+        from .portable_quantizer.quant_modules import QuantAct
         cfg = tuple((a.percentile, a.quant_mode, a.full_precision_flag, a.activation_bit, a.running_stat,
                      getattr(a, "global_range", False)) for a in self.__dict__["_fused_acts"])
         key = (tuple(x.shape), cfg)
-        cache = self.__dict__.setdefault("_fused_ok_cache", {})
-        if key not in cache:
-            Nb, _, R, R2 = x.shape
-            stem = self.layer0[0].conv if hasattr(self.layer0[0], "conv") else self.layer0[0]
-            down = stem.stride[0] * (2 if any(isinstance(m, nn.MaxPool2d) for m in self.layer0.modules()) else 1)
-            h, w = R // (down * 8), R2 // (down * 8)
-            ok = (R % (down * 8) == 0 and R2 % (down * 8) == 0 and h > 0 and w > 0
-                  and pipeline.FusedHotPath.supported(self.deconv_layers, (Nb, self.channels[4], h, w))
-                  and pipeline.FusedHeads.supported({hd: getattr(self, hd) for hd in self.heads}))
-            if not ok:
-                import warnings
-                warnings.warn("codenet_amd: enable_fused() does not cover this model configuration / input "
-                              "shape %s; running the module-by-module path (the deform stages alone stay on the "
-                              "fused schedule where it implements them, e.g. --act-percentile)" % (tuple(x.shape),))
-            cache[key] = ok
-        return cache[key]
-
-    def forward(self, x):
-        if getattr(self, "_fused", False) and x.is_cuda and not torch.is_grad_enabled() \
-                and self._fused_ok(x):
-            from . import pipeline
+        plans = self.__dict__["_plans"]
+        if key in plans:
+            return plans[key]
+        Nb, _, R, R2 = x.shape
+        stem = self.layer0[0].conv if hasattr(self.layer0[0], "conv") else self.layer0[0]
+        down = stem.stride[0] * (2 if any(isinstance(m, nn.MaxPool2d) for m in self.layer0.modules()) else 1) * 8
+        feat = (Nb, self.channels[4], -(-R // down), -(-R2 // down))        # layer4's output shape
+        plan = ("module", False, False)
+        if (R % down == 0 and R2 % down == 0 and feat[2] > 0 and feat[3] > 0
+                and pipeline.FusedHotPath.supported(self.deconv_layers, feat)
+                and pipeline.FusedHeads.supported({hd: getattr(self, hd) for hd in self.heads})):
             if self._fpath is None:
                 self._fpath = pipeline.FusedHotPath(self.deconv_layers)
+            if self._fheads is None:
                 self._fheads = pipeline.FusedHeads({h: getattr(self, h) for h in self.heads})
                 self._fbackbone = (pipeline.FusedBackbone(self)
                                    if self._fused_backbone and pipeline.FusedBackbone.supported(self) else None)
-            stages = self._fpath
-            if getattr(self, "_frozen_codes", False) and self._stage_acts_frozen() and self._frozen_planes_fit(x):
+            plan = ("fused", False, False)
+            stage_acts = [a for a in self.deconv_layers.modules() if isinstance(a, QuantAct)]
+            last = (self._frozen_codes and stage_acts and not any(a.running_stat for a in stage_acts)
+                    and pipeline.FrozenHotPath.planes_fit(self.deconv_layers, feat))
+            if last:
                 if self._ffrozen is None:
                     self._ffrozen = pipeline.FrozenHotPath(self.deconv_layers, chain_scale=True)
-                if self._fzbackbone is None and self._fbackbone is not None and self._frozen_backbone:
-                    # decided per QuantAct configuration, not once: the backbone may be frozen after the stages
-                    cfg = tuple(a.running_stat for a in self.__dict__["_fused_acts"])
-                    if self.__dict__.get("_fzbackbone_tried") != cfg:
-                        self.__dict__["_fzbackbone_tried"] = cfg
-                        if pipeline.FrozenBackbone.supported(self):
-                            self._fzbackbone = pipeline.FrozenBackbone(self)
-                stages = self._ffrozen
-                # every QuantAct of the backbone frozen too: byte codes end to end
-                if self._fzbackbone is not None and self._fzbackbone.still_frozen():
-                    # the QuantAct parameters of the stages and the heads in the backbone's first launch (once their
-                    # buffers exist: from the second call on) -- two launches fewer in the chain
-                    also, sb = None, stages._bufs
-                    hb = self._fzheads._bufs if self._fzheads is not None else None
-                    if (sb is not None and hb is not None and hb.get("acts") is not None and sb.get("acts") is not None
-                            and getattr(self, "merge_frozen_params", True)):      # (A/B switch: tools/e2e_frozen_bench.py)
-                        also = (list(sb["acts"]) + list(hb["acts"]), sb.get("sums_all"))
-                    feat8, fq, hw = self._fzbackbone(x, also=also)
-                    cov = self._fzbackbone.covered
-                    if cov is not None:
-                        stages.params_covered = cov
-                        self._fzheads.params_covered = cov
-                    r8, rq, last = stages.forward_codes(feat8, fq, hw)
-                    if r8.dtype == torch.int8:
-                        if self._fzheads is None:
-                            self._fzheads = pipeline.FusedHeads({h: getattr(self, h) for h in self.heads})
-                        if self._fzheads.codes_supported(last):          # the heads on byte codes as well
-                            return [self._fzheads.forward_codes(r8, rq, last, stages.head_flags())]
-                    return [self._fheads(*stages.expand(r8, rq, last))]
+                byte_backbone = bool(self._fbackbone is not None and self._frozen_backbone
+                                     and pipeline.FrozenBackbone.supported(self))
+                if byte_backbone and self._fzbackbone is None:
+                    self._fzbackbone = pipeline.FrozenBackbone(self)
+                byte_heads = byte_backbone and last["codes"]
+                if byte_heads and self._fzheads is None:
+                    self._fzheads = pipeline.FusedHeads({h: getattr(self, h) for h in self.heads})
+                plan = ("bytes", byte_backbone, bool(byte_heads and self._fzheads.codes_supported(last)))
+        else:
+            import warnings
+            warnings.warn("codenet_amd: enable_fused() does not cover this model configuration / input "
+                          "shape %s; running the module-by-module path (the deform stages alone stay on the "
+                          "fused schedule where it implements them, e.g. --act-percentile)" % (tuple(x.shape),))
+            if pipeline.FusedHotPath.supported(self.deconv_layers, feat):
+                if self._fpath is None:
+                    self._fpath = pipeline.FusedHotPath(self.deconv_layers)
+                plan = ("stages", False, False)
+        plans[key] = plan
+        return plan
+
+    def forward(self, x):
+        fused = getattr(self, "_fused", False) and x.is_cuda and not torch.is_grad_enabled()
+        schedule, byte_backbone, byte_heads = self._plan(x) if fused else ("module", False, False)
+        if byte_backbone:            # byte codes from the image to the heads
+            stages, fz = self._ffrozen, self._fzbackbone
+            # the QuantAct parameters of the stages and the heads in the backbone's first launch (once their buffers
+            # exist: from the second call on) -- two launches fewer in the chain
+            also, sb = None, stages._bufs
+            hb = self._fzheads._bufs if self._fzheads is not None else None
+            if (sb is not None and hb is not None and hb.get("acts") is not None and sb.get("acts") is not None
+                    and getattr(self, "merge_frozen_params", True)):      # (A/B switch: tools/e2e_frozen_bench.py)
+                also = (list(sb["acts"]) + list(hb["acts"]), sb.get("sums_all"))
+            feat8, fq, hw = fz(x, also=also)
+            r8, rq, last = stages.forward_codes(feat8, fq, hw, covered=fz.covered)
+            if byte_heads:
+                return [self._fzheads.forward_codes(r8, rq, last, stages.head_flags(), covered=fz.covered)]
+            return [self._fheads(*stages.expand(r8, rq, last))]
+        if schedule in ("fused", "bytes"):
             if self._fbackbone is not None:       # W4A8: the whole network on the HIP kernels
+                stages = self._ffrozen if schedule == "bytes" else self._fpath
                 feat, fq, hw = self._fbackbone(x)       # hw None: an NCHW tensor (odd channel count)
                 return [self._fheads(*stages.forward_nhwc(feat, fq, hw))]
             x = self.layer4(self.layer3(self.layer2(self.layer1(self.layer0(x)))))
             return [self._fheads(*self._fpath.forward_nhwc(x))]
         x = self.layer4(self.layer3(self.layer2(self.layer1(self.layer0(x)))))
-        if getattr(self, "_fused", False) and x.is_cuda and not torch.is_grad_enabled() and self._stages_fused_ok(x):
-            # enable_fused() on a configuration the fused heads / backbone do not implement (--act-percentile): the three
-            # deform stages still run on the fused schedule (one C call per stage + unpack), the rest module by module
-            from . import pipeline
-            if self._fpath is None:
-                self._fpath = pipeline.FusedHotPath(self.deconv_layers)
+        if schedule == "stages":      # one C call per stage + unpack, the rest module by module
             x = self._fpath(x)
-            return [{head: getattr(self, head)(x) for head in self.heads}]
-        from .functions.codenet_stage import forward_stage_blocks
-        x = forward_stage_blocks(self.deconv_layers, x)      # == self.deconv_layers(x); fused blocks in the QAT step
+        else:
+            from .functions.codenet_stage import forward_stage_blocks
+            x = forward_stage_blocks(self.deconv_layers, x)      # == self.deconv_layers(x); fused blocks in the QAT step
         return [{head: getattr(self, head)(x) for head in self.heads}]
-
-    def _frozen_planes_fit(self, x):
-        """The byte-code schedules need every stage's stored plane in LDS; larger inputs keep the fp32 fused schedule
-        (frozen ranges included).  Cached per input shape."""
-        from . import pipeline
-        key = ("fzfit", tuple(x.shape))
-        cache = self.__dict__.setdefault("_fused_ok_cache", {})
-        if key not in cache:
-            Nb, _, R, R2 = x.shape
-            stem = self.layer0[0].conv if hasattr(self.layer0[0], "conv") else self.layer0[0]
-            down = stem.stride[0] * (2 if any(isinstance(m, nn.MaxPool2d) for m in self.layer0.modules()) else 1) * 8
-            cache[key] = bool(pipeline.FrozenHotPath.planes_fit(self.deconv_layers,
-                                                                (Nb, self.channels[4], R // down, R2 // down)))
-        return cache[key]
-
-    def _stages_fused_ok(self, feat):
-        from . import pipeline
-        cfg = tuple((a.percentile, a.quant_mode, a.full_precision_flag, a.activation_bit, a.running_stat,
-                     getattr(a, "global_range", False)) for a in self.__dict__.get("_fused_acts", ()))
-        key = ("stages", tuple(feat.shape), cfg)
-        cache = self.__dict__.setdefault("_fused_ok_cache", {})
-        if key not in cache:
-            cache[key] = bool(pipeline.FusedHotPath.supported(self.deconv_layers, tuple(feat.shape)))
-        return cache[key]
 
 
 def fill_state_dict_(model, seed=317):

@@ -325,14 +325,15 @@ class FusedHeads:
                 return False
         return True
 
-    def forward_codes(self, r8, r_qstate, shape, overflow):
+    def forward_codes(self, r8, r_qstate, shape, overflow, covered=None):
         """The heads on the BYTE CODES of the last deform stage (``FrozenHotPath.forward_codes``), every QuantAct
         frozen: per head the int8 pointwise kernel on codes (cdn_codenet_pointwise_q8_forward: exact integer sums,
         the codes of quant_act1 written as bytes) and the row-streaming tail reading those bytes
         (cdn_codenet_head_tail_small_q8_forward); no range passes, no fp32 copy of the stage output or of y1.
         Same values as ``__call__`` on the expanded codes with the same frozen states (the first 1x1 conv is the same
         integer sum; the tail decodes a code to the value its fp32 form fake-quantises to).  `overflow`: an OverflowFlags
-        (word 2i: head i's y1 codes, word 2i + 1: its tail) or an int32 tensor (one word for everything)."""
+        (word 2i: head i's y1 codes, word 2i + 1: its tail) or an int32 tensor (one word for everything).  covered: what
+        THIS call's FrozenBackbone launch covered (FrozenHotPath.forward_codes); None: the heads launch their own parameters."""
         import ctypes
         from .. import _native as N_
         dev = r8.device
@@ -360,8 +361,7 @@ class FusedHeads:
         M = Nb * Hs * Ws
         main = torch.cuda.current_stream(dev)
         bits, _, _ = uniform_act_settings(acts, "FusedHeads.forward_codes")
-        cov, self.params_covered = getattr(self, "params_covered", None), None
-        if not (cov is not None and set(id(a) for a in acts) <= set(cov[0])):      # (else: FrozenBackbone's first launch)
+        if not (covered is not None and set(id(a) for a in acts) <= set(covered[0])):      # (else: FrozenBackbone's first launch)
             N_.check(lib.cdn_quantact_frozen_params(len(acts), *B["p"], bits, main.cuda_stream),
                      "cdn_quantact_frozen_params")
         ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731

@@ -125,31 +125,25 @@ def calibrate_serving(model, batches, margin=0.02, grow=0.04, max_iter=40, sigma
     covered = cover_frozen_ranges(model, batches, margin=0.0, spread=spread)
     span0 = {id(a): float(a.x_max.reshape(()) - a.x_min.reshape(())) for a in acts}
     model.enable_fused(frozen_codes=True)
-    # attribution needs one launch per QuantAct: the depthwise-into-pointwise fusion of the byte backbone writes two
-    # QuantActs' codes from one launch (bit-identical to the two kernels), so it is off while calibrating
     hits, widened, iters = {}, set(), 0
 
-    def one_pass():
-        with torch.no_grad():
-            for b in batches:
-                model(b)
-        fz = getattr(model, "_fzbackbone", None)
-        bad = []
-        for f in (getattr(model, "_ffrozen", None), fz):
-            if f is not None and f._bufs is not None:
-                for a in f._bufs["overflow"].acts():
-                    if all(a is not b_ for b_ in bad):
-                        bad.append(a)
-        return bad
+    # attribution needs one launch per QuantAct: the depthwise-into-pointwise fusion of the byte backbone writes two
+    # QuantActs' codes from one launch (bit-identical to the two kernels), so it is off while calibrating
+    def fuse_dwpw(flag):            # -> whether the model runs a byte-code backbone
+        fz = model.byte_backbone()
+        if fz is not None:
+            fz.fuse_dwpw = flag
+        return fz is not None
 
     def until_clean():
         nonlocal iters
         while iters < max_iter:
             iters += 1
-            fz = getattr(model, "_fzbackbone", None)
-            if fz is not None:
-                fz.fuse_dwpw = False
-            bad = one_pass()
+            fuse_dwpw(False)
+            with torch.no_grad():
+                for b in batches:
+                    model(b)
+            bad = model.overflowed_acts()
             if not bad:
                 return True
             for a in bad:
@@ -174,17 +168,15 @@ def calibrate_serving(model, batches, margin=0.02, grow=0.04, max_iter=40, sigma
                         a.x_min.sub_(sigmas * s_lo)
             clean = until_clean()
     finally:
-        fz = getattr(model, "_fzbackbone", None)
-        if fz is not None:
-            fz.fuse_dwpw = True                 # (also when a calibration pass raised)
-    if fz is not None:
+        byte_backbone = fuse_dwpw(True)         # (also when a calibration pass raised)
+    if byte_backbone:
         with torch.no_grad():
             for b in batches:               # the serving configuration itself (fused depthwise) must be clean too
                 model(b)
         clean = clean and not model.frozen_overflowed()
     widening = [float(a.x_max.reshape(()) - a.x_min.reshape(())) / max(span0[id(a)], 1e-12) for a in acts if span0[id(a)] > 0]
     return {"iterations": iters, "covered_on_module_path": covered, "widened_on_byte_schedule": len(widened),
-            "clean": bool(clean), "byte_backbone": fz is not None, "calibration_batches": len(batches),
+            "clean": bool(clean), "byte_backbone": byte_backbone, "calibration_batches": len(batches),
             "sigmas": float(sigmas) if spread is not None else 0.0, "margin": float(margin),
             "mean_widening": (sum(widening) / len(widening)) if widening else 1.0,
             "max_widening": max(widening) if widening else 1.0}
@@ -242,22 +234,25 @@ class FrozenHotPath:
 
     @staticmethod
     def planes_fit(deconv_layers, input_shape):
-        """True when every stage's stored plane fits the LDS-resident gather -- the byte-code entry points' own limit
-        (cdn_codenet_stage_supported).  Above it (inputs beyond ~1100 px) the fp32 fused schedule, which honours frozen
-        ranges too and gathers large planes from global memory, is the one to use: a byte-code stage cannot hand its
-        codes to an fp32-schedule stage."""
+        """The last stage's geometry -- dict(C, Co, H, W, codes) as in forward_codes' shape dict, codes: it leaves byte
+        codes -- when every stage's stored plane fits the LDS-resident gather -- the byte-code entry points' own limit
+        (cdn_codenet_stage_supported) --, else None.  Above it (inputs beyond ~1100 px) the fp32 fused schedule, which
+        honours frozen ranges too and gathers large planes from global memory, is the one to use: a byte-code stage
+        cannot hand its codes to an fp32-schedule stage."""
         from .. import _native as N_
         mods = list(deconv_layers)
         Nb, C, H, W = input_shape
+        last = None
         for i in range(0, len(mods), 3):
             up = 0 if i == 0 else 1
             if C % 4:      # no byte-code form (CoDeNet2x stage 0): that stage runs on the fp32 frozen schedule, NCHW input
                 if up or not N_.lib().cdn_codenet_stage_fused_supported(Nb, C, H, W, 0, 0):
-                    return False
+                    return None
             elif not N_.lib().cdn_codenet_stage_supported(Nb, C, H, W, 1, up):
-                return False
-            C, H, W = mods[i].quant_conv_channel_bn.conv.out_channels, 2 * H, 2 * W
-        return True
+                return None
+            last = dict(C=C, Co=mods[i].quant_conv_channel_bn.conv.out_channels, H=H, W=W, codes=C % 4 == 0)
+            C, H, W = last["Co"], 2 * H, 2 * W
+        return last
 
     def _acts(self, st):
         return (st[0].quant_act[1], st[0].quant_identity_deform, st[1][1])
@@ -315,9 +310,11 @@ class FrozenHotPath:
         """the flag words the byte-code heads number from 0 (FusedHeads.forward_codes)"""
         return self._bufs["overflow"].slice(len(self.stages))
 
-    def forward_codes(self, x, x_qstate=None, hw=None):
+    def forward_codes(self, x, x_qstate=None, hw=None, covered=None):
         """-> (r8 [N, H*W, Co] int8 codes of the last stage's output QuantAct (or the fp32 tensor when that stage
-        had to run on the fp32 schedule), r_state pointer, the stage's shape dict).  Input as FusedHotPath.forward_nhwc."""
+        had to run on the fp32 schedule), r_state pointer, the stage's shape dict).  Input as FusedHotPath.forward_nhwc.
+        covered: what THIS call's FrozenBackbone launch covered (its ``covered``) -- when it names these QuantActs and
+        this schedule's scale sums, their parameters and the clear were in that launch; else this call launches its own."""
         from .. import _native as N_
         nhwc_in = hw is not None
         codes_in = x.dtype == torch.int8       # byte codes of the QuantAct whose state is x_qstate (a frozen backbone)
@@ -360,8 +357,7 @@ class FrozenHotPath:
         bits, _, _ = uniform_act_settings(B["acts"], "FrozenHotPath (all stages)")
         # (scale, zero-point) of all nine frozen QuantActs from their range buffers: one launch per step
         sa = B["sums_all"]
-        cov, self.params_covered = getattr(self, "params_covered", None), None
-        if not (cov is not None and cov[1] is sa and set(id(a) for a in B["acts"]) <= set(cov[0])):
+        if not (covered is not None and covered[1] is sa and set(id(a) for a in B["acts"]) <= set(covered[0])):
             # (not derived and cleared by the backbone's first launch, FrozenBackbone.__call__(also=...): this schedule's own)
             N_.check(lib.cdn_quantact_frozen_params_clear(B["n_acts"], B["p_min"], B["p_max"], B["p_state"], bits,
                                                           sa.data_ptr() if sa is not None else None,

@@ -493,7 +493,8 @@ class QuantDeformConvWithOffsetScaleBoundPositive(Module):
         """pre_w (forward_stage_blocks only): (w_scale_q, w_dw_q, w_pw_q, b_pw) already prepared -- with the other stages'
         in one launch each -- for the native training path; None entries are prepared here.
         want_range (functions/codenet_stage.forward_stage_blocks only): on the native training path return
-        (y, per-workgroup {min, max} pairs of y) for the QuantAct of the block behind the stage.  x_up (the same caller,
+        (y, per-workgroup {min, max} pairs of y) for the QuantAct of the block behind the stage (codenet_stage:
+        range_committed).  x_up (the same caller,
         training path only): x is the STORED tensor whose nearest x2 up-sampling is the stage's input."""
         if x_up and not self._train_path_ok(x):
             raise NotImplementedError("x_up is a training-path argument of forward_stage_blocks")
