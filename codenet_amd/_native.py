@@ -222,3 +222,10 @@ def check(rc, what):
         err = NativeError("%s failed (cdn_status %d): %s" % (what, rc, last_error()))
         err.status = rc
         raise err
+
+
+def aligned_workspace(t):
+    """(pointer, bytes) of the workspace the library gets from the tensor `t`: its first 256-byte boundary and the
+    whole 256-byte blocks from there to the end of `t`."""
+    p = (t.data_ptr() + 255) // 256 * 256
+    return p, (t.numel() * t.element_size() - (p - t.data_ptr())) // 256 * 256

@@ -386,7 +386,7 @@ def ctdet_decode_native(heat, wh, reg=None, cat_spec_wh=False, K=100, apply_sigm
     # the raw pointer, so its owner must outlive the graph: capture_process keeps it in the replay closure)
     stream = torch.cuda.current_stream(heat.device)
     ws = (bufs if bufs is not None else _default_bufs).workspace(heat.device, need, stream)
-    ws_ptr = (ws.data_ptr() + 255) // 256 * 256
+    ws_ptr = N_.aligned_workspace(ws)[0]
     dets = torch.empty(B, K, 6, device=heat.device)
     rc = lib.cdn_ctdet_decode(heat.data_ptr(), wh.data_ptr(), reg.data_ptr() if reg is not None else None,
                               B, cat, H, W, int(bool(cat_spec_wh)), K, int(bool(apply_sigmoid)),

@@ -301,7 +301,7 @@ def codenet_pointwise(d, w_pw, bias=None, ep_scale=None, ep_shift=None, relu=Fal
             and lib.cdn_codenet_pointwise_i8_supported(Nb, C, Co, H * W)):
         need = lib.cdn_codenet_pointwise_i8_workspace_bytes(Nb, C, Co, H * W)
         ws = torch.empty(need + 256, dtype=torch.uint8, device=d.device)
-        wp = (ws.data_ptr() + 255) // 256 * 256
+        wp = N_.aligned_workspace(ws)[0]
         bp = _p(bias.contiguous() if bias is not None else None)
         if update_act is not None and FUSE_RANGE_UPDATE:
             # update_act = (QuantAct behind y, relu_range): updated by the launch's last workgroup; no partials
@@ -377,7 +377,7 @@ def kth_values(x, k_lo, k_hi):
     lib = N_.lib()
     need = lib.cdn_kth_values_workspace_bytes()
     ws = torch.empty(need // 4 + 64, dtype=torch.int32, device=x.device)
-    wp = (ws.data_ptr() + 255) // 256 * 256
+    wp = N_.aligned_workspace(ws)[0]
     out = torch.empty(2, device=x.device)
     rc = lib.cdn_kth_values(_p(x), x.numel(), int(k_lo), int(k_hi), out.data_ptr(), out.data_ptr() + 4, wp, need,
                             _stream(x))

@@ -3,11 +3,17 @@
 Part of codenet_amd.pipeline (split by concern in round 6; `from codenet_amd import pipeline` exposes every name as
 before)."""
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 
 from .common import (act_fusable)
+
+
+# where a backbone launch runs: the stream, the workspace (256-byte aligned pointer, bytes) whose arrival counters it
+# uses, the device of its QuantAct states
+Launch = namedtuple("Launch", "stream ws_ptr ws_bytes dev")
 
 
 class FusedBackbone:
@@ -110,7 +116,7 @@ class FusedBackbone:
                 cache[key] = (w, ((b0 - bn.running_mean) * sf + bn.bias).contiguous())
         return cache[key]
 
-    def _pw(self, a_ptr, a_q, M, lda, convbn, relu, act, out, ldo):
+    def _pw(self, ctx, a_ptr, a_q, M, lda, convbn, relu, act, out, ldo):
         from .. import _native as N_
         w, b = self._folded(convbn)
         Co, C = w.shape[0], w.shape[1]
@@ -121,23 +127,23 @@ class FusedBackbone:
         w2 = w.reshape(Co, C)
         rc = N_.lib().cdn_codenet_pointwise_nhwc_forward(
             a_ptr, a_q, M, C, Co, lda, ldo, w2.data_ptr(), ptr(i8[0]), ptr(i8[1]), ptr(i8[2]), ptr(b),
-            None, None, int(relu), *self._act_args(act, out.device), self._ws_ptr, self._ws_bytes,
-            out.data_ptr(), self._stream)
+            None, None, int(relu), *self._act_args(act, out.device), ctx.ws_ptr, ctx.ws_bytes,
+            out.data_ptr(), ctx.stream)
         N_.check(rc, "cdn_codenet_pointwise_nhwc_forward")
 
-    def _dw(self, a, a_q, N, C, H, W, stride, ld_in, convbn, act, out, ld_out):
+    def _dw(self, ctx, a, a_q, N, C, H, W, stride, ld_in, convbn, act, out, ld_out):
         from .. import _native as N_
         w, b = self._folded(convbn)
         rc = N_.lib().cdn_codenet_dw3x3_nhwc_forward(
             a.data_ptr(), a_q, N, C, H, W, 0, stride, ld_in, ld_out, w.reshape(C, 9).data_ptr(), b.data_ptr(),
-            None, None, 0, *self._act_args(act, out.device), self._ws_ptr, self._ws_bytes, out.data_ptr(),
-            self._stream)
+            None, None, 0, *self._act_args(act, out.device), ctx.ws_ptr, ctx.ws_bytes, out.data_ptr(),
+            ctx.stream)
         N_.check(rc, "cdn_codenet_dw3x3_nhwc_forward")
 
-    def _il(self, srcA, ldA, qA, srcB, ldB, qB, M, h, dst, ld_dst):
+    def _il(self, ctx, srcA, ldA, qA, srcB, ldB, qB, M, h, dst, ld_dst):
         from .. import _native as N_
         rc = N_.lib().cdn_codenet_interleave_forward(srcA, ldA, qA, srcB, ldB, qB, M, h, dst.data_ptr(),
-                                                     ld_dst, self._stream)
+                                                     ld_dst, ctx.stream)
         N_.check(rc, "cdn_codenet_interleave_forward")
 
     # -- buffers -----------------------------------------------------------------------------------
@@ -188,21 +194,19 @@ class FusedBackbone:
         return L["t1s2"]
 
     def _prepare(self, dev):
+        """The Launch an entry point issues its kernels with: the current stream and the main set of arrival counters."""
         from .. import _native as N_
         if self.__dict__.get("_ws") is None or self._ws.device != dev:
             aux = N_.lib().cdn_codenet_aux_workspace_bytes()
             self._ws = torch.zeros(aux // 4 + 64, device=dev)          # arrival counters start at zero
-        self._ws_ptr = (self._ws.data_ptr() + 255) // 256 * 256
-        self._ws_bytes = (self._ws.numel() * 4 - (self._ws_ptr - self._ws.data_ptr())) // 256 * 256
-        self._stream = torch.cuda.current_stream(dev).cuda_stream
-        self._dev = dev
+        return Launch(torch.cuda.current_stream(dev).cuda_stream, *N_.aligned_workspace(self._ws), dev)
 
     def run_units(self, nodes, x, x_ld, x_q, Nb, H, W):
         """A chain of QuantBaseNode units (first one may be stride 2) sharing their block-output QuantAct.
         x: channels-last [Nb*H*W, x_ld] holding PRE-quantisation values with QuantAct state pointer x_q,
         or final values (x_q None).  Returns (y [Nb*Ho*Wo, C] final values, C, Ho, Wo)."""
         dev = x.device
-        self._prepare(dev)
+        ctx = self._prepare(dev)
         units = [self._unit(n) for n in nodes]
         for u_ in units:          # the QuantActs' device states exist before branch 1 forks to the side stream (a state is
             for k_ in ("a1", "a2", "a4", "sh"):     # created by a fill on the CURRENT stream: see FusedHeads.forward)
@@ -219,24 +223,24 @@ class FusedBackbone:
                 sh = u["sh"]                              # the layer's shared block-output QuantAct (W4A8)
                 if node.stride == 2:
                     # branch 1 (reference order: first): dw s2 -> QuantAct -> pw -> ReLU -> shared QuantAct
-                    self._dw(x, x_q, Nb, cin, L["Hin"], L["Win"], 2, x_ld, u["c4"], u["a4"], L["t4"],
+                    self._dw(ctx, x, x_q, Nb, cin, L["Hin"], L["Win"], 2, x_ld, u["c4"], u["a4"], L["t4"],
                              L["t4"].shape[1])
-                    self._pw(L["t4"].data_ptr(), qptr(u["a4"]), Mo, L["t4"].shape[1], u["c5"], True, sh,
+                    self._pw(ctx, L["t4"].data_ptr(), qptr(u["a4"]), Mo, L["t4"].shape[1], u["c5"], True, sh,
                              L["t5"], ldh)
-                    self._il(L["t5"].data_ptr(), ldh, qptr(sh), None, 0, None, Mo, h, y, C)
+                    self._il(ctx, L["t5"].data_ptr(), ldh, qptr(sh), None, 0, None, Mo, h, y, C)
                     # branch 2: pw -> ReLU -> QuantAct -> dw s2 -> QuantAct -> pw -> ReLU -> shared QuantAct
-                    self._pw(x.data_ptr(), x_q, Mi, x_ld, u["c1"], True, u["a1"], self._t1s2(L), ldh)
-                    self._dw(L["t1s2"], qptr(u["a1"]), Nb, h, L["Hin"], L["Win"], 2, ldh, u["c2"], u["a2"],
+                    self._pw(ctx, x.data_ptr(), x_q, Mi, x_ld, u["c1"], True, u["a1"], self._t1s2(L), ldh)
+                    self._dw(ctx, L["t1s2"], qptr(u["a1"]), Nb, h, L["Hin"], L["Win"], 2, ldh, u["c2"], u["a2"],
                              L["t2"], ldh)
-                    self._pw(L["t2"].data_ptr(), qptr(u["a2"]), Mo, ldh, u["c3"], True, sh, L["t3"], ldh)
-                    self._il(None, 0, None, L["t3"].data_ptr(), ldh, qptr(sh), Mo, h, y, C)
+                    self._pw(ctx, L["t2"].data_ptr(), qptr(u["a2"]), Mo, ldh, u["c3"], True, sh, L["t3"], ldh)
+                    self._il(ctx, None, 0, None, L["t3"].data_ptr(), ldh, qptr(sh), Mo, h, y, C)
                 else:
                     # x holds FINAL values; x1 = x[:, :h] passes through, x2 = x[:, h:] is a strided view
-                    self._pw(x.data_ptr() + 4 * h, None, Mo, C, u["c1"], True, u["a1"], L["t1"], ldh)
-                    self._dw(L["t1"], qptr(u["a1"]), Nb, h, L["H"], L["W"], 1, ldh, u["c2"], u["a2"], L["t2"],
+                    self._pw(ctx, x.data_ptr() + 4 * h, None, Mo, C, u["c1"], True, u["a1"], L["t1"], ldh)
+                    self._dw(ctx, L["t1"], qptr(u["a1"]), Nb, h, L["H"], L["W"], 1, ldh, u["c2"], u["a2"], L["t2"],
                              ldh)
-                    self._pw(L["t2"].data_ptr(), qptr(u["a2"]), Mo, ldh, u["c3"], True, sh, L["t3"], ldh)
-                    self._il(x.data_ptr(), C, None, L["t3"].data_ptr(), ldh, qptr(sh), Mo, h, y, C)
+                    self._pw(ctx, L["t2"].data_ptr(), qptr(u["a2"]), Mo, ldh, u["c3"], True, sh, L["t3"], ldh)
+                    self._il(ctx, x.data_ptr(), C, None, L["t3"].data_ptr(), ldh, qptr(sh), Mo, h, y, C)
                 x, x_ld, x_q = y, C, None
                 y, y_other = y_other, y
         return x, C, L["H"], L["W"]
@@ -377,39 +381,34 @@ class FusedBackbone:
         cache[ck] = plan
         return plan
 
-    def _fork_side(self, dev):
-        """Route the following launches to the side stream (forked from the current stream), with the
-        second set of arrival counters."""
+    def _fork_side(self, ctx):
+        """The Launch on the side stream (forked from the current stream), with the second set of arrival counters."""
         from .. import _native as N_
-        if self.__dict__.get("_side") is None or self._side.device != dev:
-            self._side = torch.cuda.Stream(dev)
+        if self.__dict__.get("_side") is None or self._side.device != ctx.dev:
+            self._side = torch.cuda.Stream(ctx.dev)
             aux = N_.lib().cdn_codenet_aux_workspace_bytes()
-            self._ws2 = torch.zeros(aux // 4 + 64, device=dev)
-        self._side.wait_stream(torch.cuda.current_stream(dev))
-        self._main_launch = (self._stream, self._ws_ptr, self._ws_bytes)
-        p2 = (self._ws2.data_ptr() + 255) // 256 * 256
-        self._stream, self._ws_ptr = self._side.cuda_stream, p2
-        self._ws_bytes = (self._ws2.numel() * 4 - (p2 - self._ws2.data_ptr())) // 256 * 256
-        return True
+            self._ws2 = torch.zeros(aux // 4 + 64, device=ctx.dev)
+        self._side.wait_stream(torch.cuda.current_stream(ctx.dev))
+        return Launch(self._side.cuda_stream, *N_.aligned_workspace(self._ws2), ctx.dev)
 
-    def _leave_side(self, dev):
-        """Back to the main stream; returns the event that marks the end of the side-stream work."""
+    def _leave_side(self, side):
+        """The event that marks the end of the work launched on `side`, the Launch _fork_side returned.  A Launch holds
+        only the raw stream handle, so the event is recorded on the stream object behind it, self._side."""
         ev = torch.cuda.Event()
         ev.record(self._side)
-        self._stream, self._ws_ptr, self._ws_bytes = self._main_launch
         return ev
 
-    def _pw_raw(self, a_ptr, a_q, a_gen, M, lda, Wt, relu, act, state_ptr, out_map, out_ptr, ldo, n_gens=0):
+    def _pw_raw(self, ctx, a_ptr, a_q, a_gen, M, lda, Wt, relu, act, state_ptr, out_map, out_ptr, ldo, n_gens=0):
         """n_gens: the number of QuantAct states behind a_q when a_gen names them (0: unknown) -- the streaming kernel then
         loads them all in the round trip of the generation bytes (cdn_codenet_pointwise_mixed_forward_n)."""
         from .. import _native as N_
-        aa = self._act_args(act, self._dev)
+        aa = self._act_args(act, ctx.dev)
         if state_ptr is not None:
             aa[2] = state_ptr
         rc = N_.lib().cdn_codenet_pointwise_mixed_forward_n(
             a_ptr, a_q, a_gen, n_gens if (a_gen and self.preload_states) else 0, M, Wt["K"], Wt["Co"], lda, ldo, Wt["w"].data_ptr(), Wt["codes"].data_ptr(),
             Wt["scale"].data_ptr(), Wt["colsum"].data_ptr(), Wt["bias"].data_ptr(), None, None, int(relu),
-            out_map, *aa, self._ws_ptr, self._ws_bytes, out_ptr, self._stream)
+            out_map, *aa, ctx.ws_ptr, ctx.ws_bytes, out_ptr, ctx.stream)
         N_.check(rc, "cdn_codenet_pointwise_mixed_forward")
 
     recompute_pw1 = True      # A/B switch (tools/e2e_native_bench.py --no-recompute)
@@ -421,23 +420,24 @@ class FusedBackbone:
         from .. import _native as N_
         return N_.lib()
 
-    def _pwdw_raw(self, x_ptr, x_q, N, cin, H, W, ld_x, Wt, act_mid, C, w, b, act_out, out, ld_out, apply_only=False):
+    def _pwdw_raw(self, ctx, x_ptr, x_q, N, cin, H, W, ld_x, Wt, act_mid, C, w, b, act_out, out, ld_out,
+                  apply_only=False):
         """1x1 conv (range-only pass -> act_mid) recomputed inside the stride-2 depthwise (-> out, range of act_out).
         apply_only: the range-only pass has been issued by the caller (`_pw_raw` with out_ptr None)."""
         from .. import _native as N_
-        am, ao = self._act_args(act_mid, self._dev), self._act_args(act_out, out.device)
+        am, ao = self._act_args(act_mid, ctx.dev), self._act_args(act_out, out.device)
         fn = N_.lib().cdn_codenet_pwdw_s2_apply if apply_only else N_.lib().cdn_codenet_pwdw_s2_forward
         rc = fn(
             x_ptr, x_q, N, cin, H, W, ld_x, Wt["w"].data_ptr(), Wt["codes"].data_ptr(), Wt["scale"].data_ptr(),
             Wt["colsum"].data_ptr(), Wt["bias"].data_ptr(), am[0], am[1], am[2], C, w.data_ptr(), b.data_ptr(), ld_out,
-            ao[0], ao[1], ao[2], ao[3], ao[4], ao[5], self._ws_ptr, self._ws_bytes, out.data_ptr(), self._stream)
+            ao[0], ao[1], ao[2], ao[3], ao[4], ao[5], ctx.ws_ptr, ctx.ws_bytes, out.data_ptr(), ctx.stream)
         N_.check(rc, "cdn_codenet_pwdw_s2_forward")
 
-    def _dw_raw(self, a_ptr, a_q, a_gen, N, C, H, W, stride, ld_in, w, b, act, out, ld_out):
+    def _dw_raw(self, ctx, a_ptr, a_q, a_gen, N, C, H, W, stride, ld_in, w, b, act, out, ld_out):
         from .. import _native as N_
         rc = N_.lib().cdn_codenet_dw3x3_mixed_forward(
             a_ptr, a_q, a_gen, N, C, H, W, 0, stride, ld_in, ld_out, w.data_ptr(), b.data_ptr(), None, None, 0,
-            *self._act_args(act, out.device), self._ws_ptr, self._ws_bytes, out.data_ptr(), self._stream)
+            *self._act_args(act, out.device), ctx.ws_ptr, ctx.ws_bytes, out.data_ptr(), ctx.stream)
         N_.check(rc, "cdn_codenet_dw3x3_mixed_forward")
 
     def run_units_mixed(self, nodes, x, x_ld, x_in, Nb, H, W):
@@ -446,7 +446,7 @@ class FusedBackbone:
         pre-quantisation values are loaded with) or the layout dict of the previous layer.  Returns the
         layout dict(t=[M, C] pre-quantisation values, logical, gen (device uint8), states, C, H, W)."""
         dev = x.device
-        self._prepare(dev)
+        ctx = self._prepare(dev)
         mixed_in = isinstance(x_in, dict)
         plan = self._mixed_plan(nodes, x_in["logical"] if mixed_in else None, dev,
                                 x_in.get("gen_list") if mixed_in else None)
@@ -478,33 +478,32 @@ class FusedBackbone:
                         # the range-only pass of the recomputed conv BEFORE the fork: beside branch 1 it took 106 us of
                         # the critical path (both stream the stem's output), alone 55; branch 1 (memory-bound) then runs
                         # beside the VALU-bound recomputing kernel, which used to have the GPU to itself
-                        self._pw_raw(x.data_ptr(), a_q, None, Mi, x_ld, P["c1"], True, u["a1"], None, None, None, 0)
-                    ev = self._fork_side(dev) if self.two_streams else None
-                    self._dw_raw(x.data_ptr(), a_q, a_gen, Nb, cin, L["Hin"], L["Win"], 2, x_ld, P["w4"], P["b4"],
+                        self._pw_raw(ctx, x.data_ptr(), a_q, None, Mi, x_ld, P["c1"], True, u["a1"], None, None, None, 0)
+                    side = self._fork_side(ctx) if self.two_streams else ctx
+                    self._dw_raw(side, x.data_ptr(), a_q, a_gen, Nb, cin, L["Hin"], L["Win"], 2, x_ld, P["w4"], P["b4"],
                                  u["a4"], t4, t4.shape[1])
-                    self._pw_raw(t4.data_ptr(), qptr(u["a4"]), None, Mo, t4.shape[1], P["c5"], True, sh,
+                    self._pw_raw(side, t4.data_ptr(), qptr(u["a4"]), None, Mo, t4.shape[1], P["c5"], True, sh,
                                  sp(P["genA"]), P["omapA"].data_ptr(), Y.data_ptr(), C)
-                    if ev is not None:
-                        ev = self._leave_side(dev)
+                    ev = self._leave_side(side) if side is not ctx else None
                     if recompute:
                         # layer 1: the 1x1 conv (K = 24) recomputed inside the stride-2 depthwise -- its 58-channel
                         # fp32 output at input resolution (243 MB at batch 64, 512 x 512) is never stored
-                        self._pwdw_raw(x.data_ptr(), a_q, Nb, cin, L["Hin"], L["Win"], x_ld, P["c1"], u["a1"], h,
+                        self._pwdw_raw(ctx, x.data_ptr(), a_q, Nb, cin, L["Hin"], L["Win"], x_ld, P["c1"], u["a1"], h,
                                        P["w2"], P["b2"], u["a2"], L["t2"], ldh,
                                        apply_only=self.two_streams and self.range_first)
                     else:
-                        self._pw_raw(x.data_ptr(), a_q, a_gen, Mi, x_ld, P["c1"], True, u["a1"], None, None,
+                        self._pw_raw(ctx, x.data_ptr(), a_q, a_gen, Mi, x_ld, P["c1"], True, u["a1"], None, None,
                                      self._t1s2(L).data_ptr(), ldh, n_gens=x_in["states"].numel() // 8 if mixed_in else 0)
-                        self._dw_raw(L["t1s2"].data_ptr(), qptr(u["a1"]), None, Nb, h, L["Hin"], L["Win"], 2, ldh,
+                        self._dw_raw(ctx, L["t1s2"].data_ptr(), qptr(u["a1"]), None, Nb, h, L["Hin"], L["Win"], 2, ldh,
                                      P["w2"], P["b2"], u["a2"], L["t2"], ldh)
                     if ev is not None:
                         torch.cuda.current_stream(dev).wait_event(ev)
                 else:
-                    self._pw_raw(Y.data_ptr(), S.data_ptr(), P["gen_in"].data_ptr(), Mo, C, P["c1"], True,
+                    self._pw_raw(ctx, Y.data_ptr(), S.data_ptr(), P["gen_in"].data_ptr(), Mo, C, P["c1"], True,
                                  u["a1"], None, None, L["t1"].data_ptr(), ldh, n_gens=plan["ngen"])
-                    self._dw_raw(L["t1"].data_ptr(), qptr(u["a1"]), None, Nb, h, L["H"], L["W"], 1, ldh,
+                    self._dw_raw(ctx, L["t1"].data_ptr(), qptr(u["a1"]), None, Nb, h, L["H"], L["W"], 1, ldh,
                                  P["w2"], P["b2"], u["a2"], L["t2"], ldh)
-                self._pw_raw(L["t2"].data_ptr(), qptr(u["a2"]), None, Mo, ldh, P["c3"], True, sh, sp(P["genB"]),
+                self._pw_raw(ctx, L["t2"].data_ptr(), qptr(u["a2"]), None, Mo, ldh, P["c3"], True, sh, sp(P["genB"]),
                              P["omapB"].data_ptr(), Y.data_ptr(), C)
         return dict(t=Y, logical=plan["logical"], gen=plan["gen"], gen_list=plan["gen_list"], states=S, C=C,
                     H=L["H"], W=L["W"], inv=plan["inv"], gen_long=plan["gen_long"])
@@ -531,7 +530,7 @@ class FusedBackbone:
             raise NotImplementedError("FusedBackbone needs a [N,3,H,W] float32 GPU tensor")
         images = images.contiguous()
         m, dev = self.model, images.device
-        self._prepare(dev)
+        ctx = self._prepare(dev)
         Nb, _, R, R2 = images.shape
         qptr = lambda act: act._device_state(dev).data_ptr() if act is not None else None   # noqa: E731
         quant = hasattr(m.layer0[0], "folded")
@@ -555,7 +554,7 @@ class FusedBackbone:
             w0, b0 = self._folded(q0)
             rc = N_.lib().cdn_codenet_stem_forward(
                 images.data_ptr(), Nb, R, R2, 24, s0, w0.reshape(24, 27).data_ptr(), b0.data_ptr(), 1,
-                *self._act_args(act0, dev), self._ws_ptr, self._ws_bytes, B["t0"].data_ptr(), self._stream)
+                *self._act_args(act0, dev), ctx.ws_ptr, ctx.ws_bytes, B["t0"].data_ptr(), ctx.stream)
             N_.check(rc, "cdn_codenet_stem_forward")
             x, x_ld, x_q = B["t0"], 24, qptr(act0)          # pre-quantisation values + state
             pooled = (len(m.layer0[1]) == 3) if quant else (len(m.layer0) == 4)
@@ -564,7 +563,7 @@ class FusedBackbone:
                 if B.get("tp") is None or B["tp"].shape != (Nb, Hp * Wp, 24):
                     B["tp"] = torch.empty(Nb, Hp * Wp, 24, device=dev)
                 rc = N_.lib().cdn_codenet_maxpool3x3s2_nhwc_forward(x.data_ptr(), x_q, Nb, 24, H, W,
-                                                                    B["tp"].data_ptr(), self._stream)
+                                                                    B["tp"].data_ptr(), ctx.stream)
                 N_.check(rc, "cdn_codenet_maxpool3x3s2_nhwc_forward")
                 x, x_q, H, W = B["tp"], None, Hp, Wp         # final values from here on
             lay = None                                       # layout dict while the layers run unshuffled
@@ -584,19 +583,19 @@ class FusedBackbone:
                 B["out"] = torch.empty(Nb, H * W, c4, device=dev)
             if lay is not None and q4.folded_int8() is not None and x_ld <= self._MIXED_MAX_C:
                 W4 = self._l4_weights(q4, lay["logical"], dev, lay.get("gen_list"))
-                self._pw_raw(x.data_ptr(), lay["states"].data_ptr(), lay["gen"].data_ptr(), Nb * H * W, x_ld, W4,
+                self._pw_raw(ctx, x.data_ptr(), lay["states"].data_ptr(), lay["gen"].data_ptr(), Nb * H * W, x_ld, W4,
                              True, act4, None, None, B["out"].data_ptr(), c4, n_gens=lay["states"].numel() // 8)
             else:
                 if lay is not None:
                     x = self.materialize(lay).contiguous()
-                self._pw(x.data_ptr(), None, Nb * H * W, x_ld, q4, True, act4, B["out"], 0)
+                self._pw(ctx, x.data_ptr(), None, Nb * H * W, x_ld, q4, True, act4, B["out"], 0)
             if c4 % 4:
                 # the channels-last hand-over into stage 0 needs C % 4 == 0; CoDeNet2x's 2153 channels are
                 # materialised as the NCHW tensor the stage takes from a PyTorch backbone (fake-quantised)
                 if B.get("out_nchw") is None or B["out_nchw"].shape != (Nb, c4, H, W):
                     B["out_nchw"] = torch.empty(Nb, c4, H, W, device=dev)
                 rc = N_.lib().cdn_codenet_unpack_nchw(B["out"].data_ptr(), qptr(act4), B["out_nchw"].data_ptr(),
-                                                      Nb, c4, H, W, 0, self._stream)
+                                                      Nb, c4, H, W, 0, ctx.stream)
                 N_.check(rc, "cdn_codenet_unpack_nchw")
                 return B["out_nchw"], None, None
         return B["out"], qptr(act4), (H, W)

@@ -148,9 +148,7 @@ class FusedHeads:
         M = Nb * Hs * Ws
         main = torch.cuda.current_stream(r.device)
         stream = main.cuda_stream
-        ws_ptr = (B["ws"].data_ptr() + 255) // 256 * 256
-        ws_bytes = (B["ws"].numel() * 4 - (ws_ptr - B["ws"].data_ptr())) // 256 * 256
-        main_launch = (stream, ws_ptr, ws_bytes)
+        main_launch = (stream,) + N_.aligned_workspace(B["ws"])
         # the heads are independent chains (1x1 -> range pass -> tail) of kernels that do not fill the chip
         # on their own: head i > 0 runs on its own stream with its own arrival counters and y1 buffer
         use_streams = self.streams and len(self.heads) > 1
@@ -211,8 +209,8 @@ class FusedHeads:
             if B.get("y1_all") is None:
                 B["y1_all"] = torch.empty(nh, M, 64, device=r.device)
             wss = [B["ws"]] + list(B["ws_side"][:nh - 1])
-            wptr = [(w_.data_ptr() + 255) // 256 * 256 for w_ in wss]
-            wbytes = min((w_.numel() * 4 - (p_ - w_.data_ptr())) // 256 * 256 for w_, p_ in zip(wss, wptr))
+            wptr, wbytes = zip(*map(N_.aligned_workspace, wss))
+            wbytes = min(wbytes)
             P = ctypes.c_void_p * nh
             rec = ops._tic("head_pw", (C, 64 * nh, M))
             rc = lib.cdn_codenet_heads_pointwise_forward(
@@ -236,8 +234,7 @@ class FusedHeads:
                     sd, wsb, y1buf = B["side"][hi - 1], B["ws_side"][hi - 1], B["y1_side"][hi - 1]
                     forked.append(sd)
                     stream = sd.cuda_stream
-                    ws_ptr = (wsb.data_ptr() + 255) // 256 * 256
-                    ws_bytes = (wsb.numel() * 4 - (ws_ptr - wsb.data_ptr())) // 256 * 256
+                    ws_ptr, ws_bytes = N_.aligned_workspace(wsb)
                 else:
                     stream, ws_ptr, ws_bytes = main_launch
                 layers = params[name]

@@ -1,4 +1,5 @@
-"""FusedHotPath: the three deform stages as one C call per stage (running-range default; fp32 chained form).
+"""FusedHotPath: the three deform stages as one C call per stage (running-range default; fp32 chained form), and what
+FrozenHotPath shares with it: the stage walk, the per-stage parameter view, the fp32 stage call, unpack and capture.
 
 Part of codenet_amd.pipeline (split by concern in round 6; `from codenet_amd import pipeline` exposes every name as
 before)."""
@@ -8,7 +9,123 @@ import torch
 import torch.nn as nn
 
 from ..modules.dcn_deform_conv import DeformConvWithOffsetScaleBoundPositive
+from ..ops import _p as ptr
 from .common import (ACT_PERCENTILE, DEFER_RANGE, PHASE_GATHER, PHASE_POINTWISE, PHASE_SCALE, bn_affine, global_range_active, stage_int8_codes, uniform_act_settings)
+
+
+def deform_stages(deconv_layers, input_shape=None):
+    """The stages of a ``deconv_layers`` Sequential as (quantized, stages, geometry): three modules per W4A8 stage
+    (QuantDeformConvWithOffsetScaleBoundPositive, Sequential(ReLU, QuantAct), Upsample x2), four per fp32 stage
+    (DeformConvWithOffsetScaleBoundPositive, BatchNorm2d, ReLU, Upsample x2); NotImplementedError for any other structure.
+    geometry: (C, Co, H, W, up) of every stage for the NCHW input shape given -- each stage reads its predecessor's output
+    up-sampled x2 (up = 1) --, None without one."""
+    from ..portable_quantizer.quant_modules import QuantAct, QuantDeformConvWithOffsetScaleBoundPositive
+
+    def w4a8_stage(st):
+        return (isinstance(st[0], QuantDeformConvWithOffsetScaleBoundPositive) and len(st[1]) == 2
+                and isinstance(st[1][1], QuantAct))
+
+    def fp32_stage(st):
+        return (isinstance(st[0], DeformConvWithOffsetScaleBoundPositive) and isinstance(st[1], nn.BatchNorm2d)
+                and hasattr(st[0], "conv_channel"))
+
+    mods = list(deconv_layers)
+    quantized = bool(mods) and isinstance(mods[0], QuantDeformConvWithOffsetScaleBoundPositive)
+    step, stage_form = (3, w4a8_stage) if quantized else (4, fp32_stage)
+    if not mods or len(mods) % step:
+        raise NotImplementedError("deconv_layers: not a sequence of whole fused stages")
+    stages = [mods[i:i + step] for i in range(0, len(mods), step)]
+    for st in stages:
+        if not (isinstance(st[-1], nn.Upsample) and st[-1].scale_factor in (2, 2.0) and stage_form(st)):
+            raise NotImplementedError("deconv_layers: a stage the fused schedules do not implement")
+    geometry = None
+    if input_shape is not None:
+        _, C, H, W = input_shape
+        geometry = []
+        for i, st in enumerate(stages):
+            Co = st[0].quant_conv_channel_bn.conv.out_channels if quantized else st[0].out_channels
+            geometry.append((C, Co, H, W, int(i > 0)))
+            C, H, W = Co, 2 * H, 2 * W
+    return quantized, stages, geometry
+
+
+def stage_acts(st):
+    """The three QuantActs of a W4A8 stage in launch order: scale prediction, gather, stage output."""
+    return (st[0].quant_act[1], st[0].quant_identity_deform, st[1][1])
+
+
+@torch.no_grad()      # inference schedule: derived weights come from the modules' caches, never an autograd graph
+def stage_params(st, affine=None, int8=True, kblocked=True):
+    """One stage's parameters as the stage entry points take them.  W4A8: i8 / kb_flag = the pointwise conv's int8 codes
+    and layout flag (stage_int8_codes; None, 0 without int8), and scale_i8 = the scale conv's int8_form -- called by a
+    byte-code stage that chains scale sums, so the form is derived only where it is used.  fp32: BatchNorm as the
+    pointwise epilogue (bn_affine, cached in the dict `affine`)."""
+    from ..portable_quantizer.quant_modules import QuantDeformConvWithOffsetScaleBoundPositive
+    q = st[0]
+    if isinstance(q, QuantDeformConvWithOffsetScaleBoundPositive):
+        w_pw, b_pw = q.quant_conv_channel_bn.folded()
+        i8, kb_flag = stage_int8_codes(q.quant_conv_channel_bn, kblocked) if int8 else (None, 0)
+        return dict(
+            i8=i8, kb_flag=kb_flag,
+            w_scale=q.quant_conv_scale.quantized_weight().reshape(-1),
+            b_scale=q.quant_conv_scale.bias, lo=q.quant_act[0].min_val, hi=q.quant_act[0].max_val,
+            w_dw=q.quant_deform_conv.quantized_weight(), w_pw=w_pw.reshape(w_pw.size(0), -1),
+            bias=b_pw, ep_scale=None, ep_shift=None, acts=stage_acts(st), scale_i8=q.quant_conv_scale.int8_form)
+    es, eh = bn_affine(affine, st[1])
+    return dict(w_scale=q.conv_scale.weight.reshape(-1), b_scale=q.conv_scale.bias,
+                lo=q.conv_bound.min_val, hi=q.conv_bound.max_val, w_dw=q.conv.weight,
+                w_pw=q.conv_channel.weight.reshape(q.out_channels, -1), bias=None,
+                ep_scale=es, ep_shift=eh, acts=(None, None, None), i8=None, kb_flag=0)
+
+
+def act_pointers(acts, dev):
+    """x_min, x_max and device state of each QuantAct (three None for a missing one), as the stage calls take them."""
+    out = []
+    for act in acts:
+        out += [None, None, None] if act is None else [act.x_min.data_ptr(), act.x_max.data_ptr(),
+                                                       act._device_state(dev).data_ptr()]
+    return out
+
+
+def stage_fused_forward(x_ptr, flags, x_q, Nb, sb, p, act_args, ws, stream):
+    """One cdn_codenet_stage_fused_forward call: input x_ptr (layout and schedule bits in `flags`, QuantAct state x_q),
+    geometry and output sb["r"] from the stage's buffer dict, parameters from its stage_params view `p` (whose kb_flag is
+    ORed into flags), act_args = act_pointers(...) + [bits, momentum, running], ws = (pointer, bytes) of the workspace."""
+    from .. import _native as N_
+    rc = N_.lib().cdn_codenet_stage_fused_forward(
+        x_ptr, flags | p["kb_flag"], sb["up"], x_q, Nb, sb["C"], sb["Co"], sb["H"], sb["W"],
+        ptr(p["w_scale"]), ptr(p["b_scale"]), float(p["lo"]), float(p["hi"]), ptr(p["w_dw"]), ptr(p["w_pw"]),
+        *(map(ptr, p["i8"]) if p["i8"] is not None else (None, None, None)),
+        ptr(p["bias"]), ptr(p["ep_scale"]), ptr(p["ep_shift"]), 1, *act_args, *ws, sb["r"].data_ptr(), stream)
+    N_.check(rc, "cdn_codenet_stage_fused_forward")
+
+
+def unpack_nchw(r, rq, last, out):
+    """forward_nhwc's result (r, its QuantAct state rq, the last stage's shape dict) fake-quantised, up-sampled x2 and
+    written NCHW into `out`: the Sequential's output tensor."""
+    from .. import _native as N_
+    from .. import ops
+    rec = ops._tic("unpack", (last["Co"], last["H"], last["W"]))
+    rc = N_.lib().cdn_codenet_unpack_nchw(r.data_ptr(), rq, out.data_ptr(), r.shape[0], last["Co"], last["H"], last["W"],
+                                          1, torch.cuda.current_stream(r.device).cuda_stream)
+    ops._toc(rec)
+    N_.check(rc, "cdn_codenet_unpack_nchw")
+    return out
+
+
+def capture_graph(run, x):
+    """run(x) once (allocates + warms, also derives cached weights), then captured into a HIP graph over the static
+    input buffer `x`; returns a callable replaying it that returns the static output."""
+    run(x)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = run(x)
+
+    def replay():
+        g.replay()
+        return out
+    return replay
 
 
 class FusedHotPath:
@@ -21,20 +138,12 @@ class FusedHotPath:
     and can be captured into a HIP graph (``capture()``)."""
 
     def __init__(self, deconv_layers, int8_pointwise=True, kblocked_codes=True, chain_scale=True):
-        from ..portable_quantizer.quant_modules import QuantDeformConvWithOffsetScaleBoundPositive
         self.seq = deconv_layers
         self.int8_pointwise = int8_pointwise
         self.kblocked_codes = kblocked_codes      # (False: tests compare the two int8 pointwise kernels)
         self.chain_scale = chain_scale            # fp32 model: the next stage's scale prediction from the pointwise epilogue
-        mods = list(deconv_layers)
-        self.quantized = isinstance(mods[0], QuantDeformConvWithOffsetScaleBoundPositive)
-        step = 3 if self.quantized else 4
-        assert len(mods) % step == 0
-        self.stages = [mods[i:i + step] for i in range(0, len(mods), step)]
-        for st in self.stages:
-            assert isinstance(st[-1], nn.Upsample) and st[-1].scale_factor in (2, 2.0)
+        self.quantized, self.stages, _ = deform_stages(deconv_layers)
         self._bufs = None
-        self._graph = None
         self._affine = {}
         self.stage_hook = None        # diagnostics: called as stage_hook(stage_shape_dict) after each stage
 
@@ -43,80 +152,29 @@ class FusedHotPath:
         """True when the fused schedule implements this Sequential (and, given the NCHW shape of its input,
         this geometry): callers keep the module path otherwise."""
         from .. import _native as N_
-        from ..portable_quantizer.quant_modules import QuantAct, QuantDeformConvWithOffsetScaleBoundPositive
-        mods = list(deconv_layers)
-        if not mods:
+        try:
+            quantized, stages, geometry = deform_stages(deconv_layers, input_shape)
+            for st in stages if quantized else ():
+                acts = stage_acts(st)
+                uniform_act_settings(acts, "stage", allow_percentile=True, allow_global=True)
+                global_range_active(acts)              # (raises on a mixture)
+        except NotImplementedError:
             return False
-        quantized = isinstance(mods[0], QuantDeformConvWithOffsetScaleBoundPositive)
-        step = 3 if quantized else 4
-        if len(mods) % step:
-            return False
-        shape = tuple(input_shape) if input_shape is not None else None
-        for i in range(0, len(mods), step):
-            st = mods[i:i + step]
-            if not (isinstance(st[-1], nn.Upsample) and st[-1].scale_factor in (2, 2.0)):
-                return False
-            if quantized:
-                if not (isinstance(st[0], QuantDeformConvWithOffsetScaleBoundPositive) and len(st[1]) == 2
-                        and isinstance(st[1][1], QuantAct)):
-                    return False
-                acts = (st[0].quant_act[1], st[0].quant_identity_deform, st[1][1])
-                try:
-                    uniform_act_settings(acts, "stage", allow_percentile=True, allow_global=True)
-                    global_range_active(acts)              # (raises on a mixture)
-                except NotImplementedError:
-                    return False
-                cout = st[0].quant_conv_channel_bn.conv.out_channels
-            else:
-                if not (isinstance(st[0], DeformConvWithOffsetScaleBoundPositive)
-                        and isinstance(st[1], nn.BatchNorm2d) and hasattr(st[0], "conv_channel")):
-                    return False
-                cout = st[0].out_channels
-            if shape is not None:
-                Nb, C, H, W = shape
-                up = 0 if i == 0 else 1
-                if not N_.lib().cdn_codenet_stage_fused_supported(Nb, C, H, W, 0 if i == 0 else 1, up):
-                    return False
-                shape = (Nb, cout, 2 * H, 2 * W)
-        return True
+        return geometry is None or all(N_.lib().cdn_codenet_stage_fused_supported(input_shape[0], C, H, W, up, up)
+                                       for C, _, H, W, up in geometry)
 
-    # -- per-stage parameter views -------------------------------------------------------------
-    @torch.no_grad()      # inference schedule: derived weights come from the modules' caches, never an autograd graph
     def _stage_params(self, st):
-        if self.quantized:
-            q, post = st[0], st[1]
-            w_pw, b_pw = q.quant_conv_channel_bn.folded()
-            i8, kb_flag = (stage_int8_codes(q.quant_conv_channel_bn, self.kblocked_codes) if self.int8_pointwise
-                           else (None, 0))
-            return dict(
-                i8=i8, kb_flag=kb_flag,
-                w_scale=q.quant_conv_scale.quantized_weight().reshape(-1),
-                b_scale=q.quant_conv_scale.bias, lo=q.quant_act[0].min_val, hi=q.quant_act[0].max_val,
-                w_dw=q.quant_deform_conv.quantized_weight(), w_pw=w_pw.reshape(w_pw.size(0), -1),
-                bias=b_pw, ep_scale=None, ep_shift=None,
-                acts=(q.quant_act[1], q.quant_identity_deform, post[1]))
-        op, bn = st[0], st[1]
-        es, eh = bn_affine(self._affine, bn)
-        return dict(w_scale=op.conv_scale.weight.reshape(-1), b_scale=op.conv_scale.bias,
-                    lo=op.conv_bound.min_val, hi=op.conv_bound.max_val, w_dw=op.conv.weight,
-                    w_pw=op.conv_channel.weight.reshape(op.out_channels, -1), bias=None,
-                    ep_scale=es, ep_shift=eh, acts=(None, None, None), i8=None, kb_flag=0)
+        return stage_params(st, self._affine, self.int8_pointwise, self.kblocked_codes)
 
     def _alloc(self, x):
         from .. import _native as N_
-        Nb, C, H, W = x.shape
+        Nb = x.shape[0]
         dev = x.device
         bufs, ws_bytes = [], 0
-        for i, st in enumerate(self.stages):
-            op = st[0]
-            cin = op.quant_deform_conv.in_channels if self.quantized else op.in_channels
-            cout = (op.quant_conv_channel_bn.conv.out_channels if self.quantized
-                    else op.out_channels)
-            up = 0 if i == 0 else 1
-            Hs, Ws = (H, W) if i == 0 else (bufs[-1]["H"] * 2, bufs[-1]["W"] * 2)
-            ws_bytes = max(ws_bytes, N_.lib().cdn_codenet_stage_workspace_bytes(Nb, cin, Hs, Ws, up))
-            bufs.append(dict(C=cin, Co=cout, H=Hs, W=Ws, up=up,
-                             r=torch.empty(Nb, Hs * Ws, cout, device=dev), parts=0, parts_buf=None))
+        for C, Co, H, W, up in deform_stages(self.seq, x.shape)[2]:
+            ws_bytes = max(ws_bytes, N_.lib().cdn_codenet_stage_workspace_bytes(Nb, C, H, W, up))
+            bufs.append(dict(C=C, Co=Co, H=H, W=W, up=up, r=torch.empty(Nb, H * W, Co, device=dev), parts=0,
+                             parts_buf=None))
         if not self.quantized and self.chain_scale:
             # chained fp32 stages (round 6): the pointwise epilogue of stage i leaves the partial sums of stage i + 1's scale
             # prediction -- no QuantAct sits between them in the fp32 model -- and stage i + 1 runs without its scale launch
@@ -131,17 +189,7 @@ class FusedHotPath:
 
     def __call__(self, x):
         """Stages + unpack: the Sequential's output tensor (NCHW, up-sampled, fake-quantised)."""
-        from .. import _native as N_
-        from .. import ops
-        cur, cur_q, last = self.forward_nhwc(x)
-        B = self._bufs
-        rec = ops._tic("unpack", (last["Co"], last["H"], last["W"]))
-        rc = N_.lib().cdn_codenet_unpack_nchw(cur.data_ptr(), cur_q, B["out"].data_ptr(), x.shape[0],
-                                              last["Co"], last["H"], last["W"], 1,
-                                              torch.cuda.current_stream(x.device).cuda_stream)
-        ops._toc(rec)
-        N_.check(rc, "cdn_codenet_unpack_nchw")
-        return B["out"]
+        return unpack_nchw(*self.forward_nhwc(x), self._bufs["out"])
 
     def forward_nhwc(self, x, x_qstate=None, hw=None):
         """The three stages WITHOUT the final materialisation: returns (r, r_qstate, shape) with r the
@@ -169,64 +217,41 @@ class FusedHotPath:
         Nb = x.shape[0]
         lib = N_.lib()
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        ws = B["ws"]
-        ws_ptr = (ws.data_ptr() + 255) // 256 * 256
-        ws_bytes = (ws.numel() * 4 - (ws_ptr - ws.data_ptr())) // 256 * 256
+        ws = N_.aligned_workspace(B["ws"])
         cur, cur_nhwc, cur_q = x, int(nhwc_in), (x_qstate if nhwc_in else None)
         with torch.no_grad():
             for si, (st, sb) in enumerate(zip(self.stages, B["stages"])):
                 p = self._stage_params(st)
-                ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-                a = []
                 bits, mom, running = uniform_act_settings(p["acts"], "FusedHotPath stage", allow_percentile=True,
                                                           allow_global=True)
                 pct = ACT_PERCENTILE if (p["acts"][0] is not None and p["acts"][0].percentile) else 0
-                for act in p["acts"]:
-                    if act is None:
-                        a += [None, None, None]
-                    else:
-                        a += [act.x_min.data_ptr(), act.x_max.data_ptr(),
-                              act._device_state(x.device).data_ptr()]
+                a = act_pointers(p["acts"], x.device)
+                flags = cur_nhwc | getattr(self, "gather_flag", 0)
                 rec = ops._tic("stage", (sb["C"], sb["H"], sb["W"]))
-
-                def stage_call_chain():
-                    nxt = B["stages"][si + 1] if si + 1 < len(B["stages"]) else None
-                    prev = B["stages"][si - 1] if si > 0 else None
-                    out_parts = sb["parts_buf"] if (nxt is not None and sb["parts"]) else None
-                    in_parts = prev["parts_buf"] if (prev is not None and prev["parts"]) else None
-                    nws = self._stage_params(self.stages[si + 1])["w_scale"] if out_parts is not None else None
-                    rc = lib.cdn_codenet_stage_fused_forward_chain(
-                        cur.data_ptr(), cur_nhwc | getattr(self, "gather_flag", 0), sb["up"], cur_q, Nb, sb["C"], sb["Co"],
-                        sb["H"], sb["W"], ptr(p["w_scale"]), ptr(p["b_scale"]), float(p["lo"]), float(p["hi"]),
-                        ptr(p["w_dw"]), ptr(p["w_pw"]), ptr(p["bias"]), ptr(p["ep_scale"]), ptr(p["ep_shift"]), 1,
-                        ws_ptr, ws_bytes, sb["r"].data_ptr(), ptr(in_parts), prev["parts"] if in_parts is not None else 0,
-                        ptr(nws), ptr(out_parts), stream)
-                    N_.check(rc, "cdn_codenet_stage_fused_forward_chain")
-
-                def stage_call(extra):
-                    rc = lib.cdn_codenet_stage_fused_forward(
-                        cur.data_ptr(), cur_nhwc | getattr(self, "gather_flag", 0) | pct | p["kb_flag"] | extra, sb["up"],
-                        cur_q, Nb, sb["C"],
-                        sb["Co"], sb["H"], sb["W"],
-                        ptr(p["w_scale"]), ptr(p["b_scale"]), float(p["lo"]), float(p["hi"]),
-                        ptr(p["w_dw"]), ptr(p["w_pw"]),
-                        *([ptr(t) for t in p["i8"]] if p["i8"] is not None else [None, None, None]),
-                        ptr(p["bias"]), ptr(p["ep_scale"]),
-                        ptr(p["ep_shift"]), 1, *a, bits, mom, running, ws_ptr, ws_bytes,
-                        sb["r"].data_ptr(), stream)
-                    N_.check(rc, "cdn_codenet_stage_fused_forward")
-
+                prev = B["stages"][si - 1] if si > 0 else None
                 if global_range_active(p["acts"]):
                     # multi-process parity mode (collective 3): the stage call split at its three
                     # QuantActs -- each producer only measures, the batch extremes are reduced over the ranks (one
                     # 8-byte MAX all-reduce of {-min, max}), the commit applies the reference's update with them
                     for phase, act in zip((PHASE_SCALE, PHASE_GATHER, PHASE_POINTWISE), p["acts"]):
-                        stage_call(DEFER_RANGE | phase)
+                        stage_fused_forward(cur.data_ptr(), flags | pct | DEFER_RANGE | phase, cur_q, Nb, sb, p,
+                                            a + [bits, mom, running], ws, stream)
                         self._global_commit(act, x.device, bits, mom, stream)
-                elif not self.quantized and cur_q is None and (sb["parts"] or (si > 0 and B["stages"][si - 1]["parts"])):
-                    stage_call_chain()
+                elif not self.quantized and cur_q is None and (sb["parts"] or (prev is not None and prev["parts"])):
+                    nxt = B["stages"][si + 1] if si + 1 < len(B["stages"]) else None
+                    out_parts = sb["parts_buf"] if (nxt is not None and sb["parts"]) else None
+                    in_parts = prev["parts_buf"] if (prev is not None and prev["parts"]) else None
+                    nws = self._stage_params(self.stages[si + 1])["w_scale"] if out_parts is not None else None
+                    rc = lib.cdn_codenet_stage_fused_forward_chain(
+                        cur.data_ptr(), flags, sb["up"], cur_q, Nb, sb["C"], sb["Co"], sb["H"], sb["W"],
+                        ptr(p["w_scale"]), ptr(p["b_scale"]), float(p["lo"]), float(p["hi"]), ptr(p["w_dw"]),
+                        ptr(p["w_pw"]), ptr(p["bias"]), ptr(p["ep_scale"]), ptr(p["ep_shift"]), 1, *ws,
+                        sb["r"].data_ptr(), ptr(in_parts), prev["parts"] if in_parts is not None else 0, ptr(nws),
+                        ptr(out_parts), stream)
+                    N_.check(rc, "cdn_codenet_stage_fused_forward_chain")
                 else:
-                    stage_call(0)
+                    stage_fused_forward(cur.data_ptr(), flags | pct, cur_q, Nb, sb, p, a + [bits, mom, running], ws,
+                                        stream)
                 ops._toc(rec)
                 if self.stage_hook is not None:
                     self.stage_hook(sb)
@@ -253,18 +278,7 @@ class FusedHotPath:
         """Capture one pass over the static input buffer `x` into a HIP graph; returns a callable
         replaying it (the output tensor is static too).  unpack=False: the three stages only, returning the
         channels-last stage-resolution tensor ``forward_nhwc`` hands to the native heads."""
-        if self.quantized and any(global_range_active(self._stage_params(st)["acts"]) for st in self.stages):
+        if self.quantized and any(global_range_active(stage_acts(st)) for st in self.stages):
             raise NotImplementedError("FusedHotPath.capture: the global-range mode runs collectives between the kernels; "
                                       "launch it eagerly")
-        run = self.__call__ if unpack else (lambda t: self.forward_nhwc(t)[0])
-        run(x)                        # allocate + warm (also derives cached weights)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = run(x)
-        self._graph = g
-
-        def replay():
-            g.replay()
-            return out
-        return replay
+        return capture_graph(self.__call__ if unpack else (lambda t: self.forward_nhwc(t)[0]), x)

@@ -8,8 +8,10 @@ import os
 import torch
 import torch.nn as nn
 
-from .common import (OverflowFlags, act_fusable, set_running_stat, stage_int8_codes, uniform_act_settings)
-from .hotpath import (FusedHotPath)
+from ..ops import _p as ptr
+from .common import (OverflowFlags, act_fusable, set_running_stat, uniform_act_settings)
+from .hotpath import (FusedHotPath, act_pointers, capture_graph, deform_stages, stage_acts, stage_fused_forward,
+                      stage_params, unpack_nchw)
 from .backbone import (FusedBackbone)
 
 
@@ -217,19 +219,16 @@ class FrozenHotPath:
     with the same code-flip tolerance, tests/test_gpu_frozen.py)."""
 
     def __init__(self, deconv_layers, chain_scale=False):
-        from ..portable_quantizer.quant_modules import QuantDeformConvWithOffsetScaleBoundPositive
         self.chain_scale = bool(chain_scale)
-        mods = list(deconv_layers)
-        if not mods or not isinstance(mods[0], QuantDeformConvWithOffsetScaleBoundPositive):
-            raise NotImplementedError("FrozenHotPath needs the W4A8 deconv_layers")
         if not FusedHotPath.supported(deconv_layers):
             raise NotImplementedError("this deconv_layers configuration is not implemented by the fused schedules")
+        quantized, self.stages, _ = deform_stages(deconv_layers)
+        if not quantized:
+            raise NotImplementedError("FrozenHotPath needs the W4A8 deconv_layers")
         self.seq = deconv_layers
-        self.stages = [mods[i:i + 3] for i in range(0, len(mods), 3)]
         for st in self.stages:
             if st[0].quant_conv_channel_bn.folded_int8() is None:
                 raise NotImplementedError("FrozenHotPath needs per-channel symmetric <= 4-bit pointwise weights")
-        self._fp32 = FusedHotPath(deconv_layers)        # fp32 frozen schedule for stages without byte codes
         self._bufs = None
 
     @staticmethod
@@ -240,34 +239,27 @@ class FrozenHotPath:
         honours frozen ranges too and gathers large planes from global memory, is the one to use: a byte-code stage
         cannot hand its codes to an fp32-schedule stage."""
         from .. import _native as N_
-        mods = list(deconv_layers)
-        Nb, C, H, W = input_shape
+        quantized, _, geometry = deform_stages(deconv_layers, input_shape)
+        if not quantized:
+            return None
+        Nb = input_shape[0]
         last = None
-        for i in range(0, len(mods), 3):
-            up = 0 if i == 0 else 1
+        for C, Co, H, W, up in geometry:
             if C % 4:      # no byte-code form (CoDeNet2x stage 0): that stage runs on the fp32 frozen schedule, NCHW input
                 if up or not N_.lib().cdn_codenet_stage_fused_supported(Nb, C, H, W, 0, 0):
                     return None
             elif not N_.lib().cdn_codenet_stage_supported(Nb, C, H, W, 1, up):
                 return None
-            last = dict(C=C, Co=mods[i].quant_conv_channel_bn.conv.out_channels, H=H, W=W, codes=C % 4 == 0)
-            C, H, W = last["Co"], 2 * H, 2 * W
+            last = dict(C=C, Co=Co, H=H, W=W, codes=C % 4 == 0)
         return last
-
-    def _acts(self, st):
-        return (st[0].quant_act[1], st[0].quant_identity_deform, st[1][1])
 
     def _alloc(self, shape, dev, nhwc_in, key):
         import ctypes
         from .. import _native as N_
-        Nb, C, H, W = shape
+        Nb = shape[0]
         lib = N_.lib()
         bufs, ws_bytes, ws32_bytes = [], 0, 0
-        for i, st in enumerate(self.stages):
-            cin = st[0].quant_deform_conv.in_channels
-            cout = st[0].quant_conv_channel_bn.conv.out_channels
-            up = 0 if i == 0 else 1
-            Hs, Ws = (H, W) if i == 0 else (bufs[-1]["H"] * 2, bufs[-1]["W"] * 2)
+        for i, (cin, cout, Hs, Ws, up) in enumerate(deform_stages(self.seq, shape)[2]):
             codes = cin % 4 == 0 and bool(lib.cdn_codenet_stage_supported(Nb, cin, Hs, Ws, 1 if (i or nhwc_in) else 0, up))
             if codes:
                 ws_bytes = max(ws_bytes, lib.cdn_codenet_stage_frozen_workspace_bytes(Nb, cin, Hs, Ws, up))
@@ -289,7 +281,7 @@ class FrozenHotPath:
                 for i, sz in zip(take, sizes):
                     bufs[i]["sums"] = sums_all[off:off + Nb * bufs[i]["H"] * bufs[i]["W"]]
                     off += sz
-        acts = [a for st in self.stages for a in self._acts(st)]
+        acts = [a for st in self.stages for a in stage_acts(st)]
         n = len(acts)
         arr = ctypes.c_void_p * n
         last = bufs[-1]
@@ -304,7 +296,7 @@ class FrozenHotPath:
             p_min=arr(*[a.x_min.data_ptr() for a in acts]), p_max=arr(*[a.x_max.data_ptr() for a in acts]),
             p_state=arr(*[a._device_state(dev).data_ptr() for a in acts]))
         for i, st in enumerate(self.stages):
-            self._bufs["overflow"].name(i, self._acts(st))
+            self._bufs["overflow"].name(i, stage_acts(st))
 
     def head_flags(self):
         """the flag words the byte-code heads number from 0 (FusedHeads.forward_codes)"""
@@ -343,7 +335,7 @@ class FrozenHotPath:
         dev = x.device
         # the cached pointer arrays name the QuantActs' range buffers: a re-assigned buffer (load_state_dict(assign=
         # True), a .to() round trip) must rebuild them, so their addresses are part of the key
-        key = (shape, dev, nhwc_in, codes_in) + tuple(p for st in self.stages for a in self._acts(st)
+        key = (shape, dev, nhwc_in, codes_in) + tuple(p for st in self.stages for a in stage_acts(st)
                                             for p in (a.x_min.data_ptr(), a.x_max.data_ptr()))
         if self._bufs is None or self._bufs["key"] != key:
             self._alloc(shape, dev, nhwc_in, key)
@@ -363,57 +355,35 @@ class FrozenHotPath:
                                                           sa.data_ptr() if sa is not None else None,
                                                           sa.numel() * 4 if sa is not None else 0, stream),
                      "cdn_quantact_frozen_params_clear")
-        ws_ptr = (B["ws"].data_ptr() + 255) // 256 * 256
-        ws_bytes = B["ws"].numel() - (ws_ptr - B["ws"].data_ptr())
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        ws_ptr = N_.aligned_workspace(B["ws"])[0]
+        ws_bytes = B["ws"].numel() - (ws_ptr - B["ws"].data_ptr())      # (all of it: not rounded down to 256 bytes)
         cur_ptr, cur_kind, cur_q = x.data_ptr(), (2 if codes_in else 1 if nhwc_in else 0), (x_qstate if nhwc_in else None)
         with torch.no_grad():
-            for st, sb in zip(self.stages, B["stages"]):
-                q = st[0]
-                a_s, a_d, a_r = self._acts(st)
-                sp = [a._device_state(dev).data_ptr() for a in (a_s, a_d, a_r)]
+            for si, (st, sb) in enumerate(zip(self.stages, B["stages"])):
+                p = stage_params(st, kblocked=not sb["codes"])
+                a = act_pointers(p["acts"], dev)
                 if sb["codes"]:
-                    (codes, scale, colsum), kb_flag = q.quant_conv_channel_bn.folded_int8(), 0
-                else:
-                    (codes, scale, colsum), kb_flag = stage_int8_codes(q.quant_conv_channel_bn)
-                w_pw, b_pw = q.quant_conv_channel_bn.folded()
-                w_sc = q.quant_conv_scale.quantized_weight().reshape(-1)
-                w_dw = q.quant_deform_conv.quantized_weight()
-                bound = q.quant_act[0]
-                if sb["codes"]:
-                    si = B["stages"].index(sb)
                     sums_in = B["stages"][si - 1]["sums"] if si > 0 and cur_kind == 2 else None
-                    sw_ptr = nsc_ptr = None
-                    if sums_in is not None:
-                        sw_ptr = q.quant_conv_scale.int8_form()[1].data_ptr()
-                    if sb["sums"] is not None:
-                        nsc_ptr = self.stages[si + 1][0].quant_conv_scale.int8_form()[0].data_ptr()
+                    # (the next stage's scale codes come from its module: its view is derived right before its own launch)
                     rc = lib.cdn_codenet_stage_frozen_chained_forward(
                         cur_ptr, cur_kind | getattr(self, "gather_flag", 0), sb["up"], cur_q, Nb, sb["C"], sb["Co"],
-                        sb["H"], sb["W"],
-                        ptr(w_sc), ptr(q.quant_conv_scale.bias), float(bound.min_val), float(bound.max_val),
-                        ptr(w_dw), ptr(codes), ptr(scale), ptr(colsum), ptr(b_pw), 1, sp[0], sp[1], sp[2],
-                        ws_ptr, ws_bytes, sb["r8"].data_ptr(), B["overflow"].ptr(si),
-                        ptr(sums_in), sw_ptr, nsc_ptr, ptr(sb["sums"]), stream)
+                        sb["H"], sb["W"], ptr(p["w_scale"]), ptr(p["b_scale"]), float(p["lo"]), float(p["hi"]),
+                        ptr(p["w_dw"]), *map(ptr, p["i8"]), ptr(p["bias"]), 1, a[2], a[5], a[8],
+                        ws_ptr, ws_bytes, sb["r8"].data_ptr(), B["overflow"].ptr(si), ptr(sums_in),
+                        p["scale_i8"]()[1].data_ptr() if sums_in is not None else None,
+                        self.stages[si + 1][0].quant_conv_scale.int8_form()[0].data_ptr() if sb["sums"] is not None
+                        else None,
+                        ptr(sb["sums"]), stream)
                     N_.check(rc, "cdn_codenet_stage_frozen_chained_forward")
-                    cur_ptr, cur_kind, cur_q = sb["r8"].data_ptr(), 2, sp[2]
+                    cur_ptr, cur_kind = sb["r8"].data_ptr(), 2
                 else:
                     if cur_kind == 2:
                         raise NotImplementedError("a byte-code stage cannot feed an fp32-schedule stage")
-                    w32 = B["ws32"]
-                    w32_ptr = (w32.data_ptr() + 255) // 256 * 256
-                    w32_bytes = (w32.numel() * 4 - (w32_ptr - w32.data_ptr())) // 256 * 256
-                    acts3 = []
-                    for a in (a_s, a_d, a_r):
-                        acts3 += [a.x_min.data_ptr(), a.x_max.data_ptr(), a._device_state(dev).data_ptr()]
-                    rc = lib.cdn_codenet_stage_fused_forward(
-                        cur_ptr, cur_kind | kb_flag, sb["up"], cur_q, Nb, sb["C"], sb["Co"], sb["H"], sb["W"],
-                        ptr(w_sc), ptr(q.quant_conv_scale.bias), float(bound.min_val), float(bound.max_val),
-                        ptr(w_dw), ptr(w_pw.reshape(w_pw.size(0), -1)), ptr(codes), ptr(scale), ptr(colsum), ptr(b_pw),
-                        None, None, 1, *acts3, bits, float(a_r.momentum), 0, w32_ptr, w32_bytes,
-                        sb["r"].data_ptr(), stream)
-                    N_.check(rc, "cdn_codenet_stage_fused_forward")
-                    cur_ptr, cur_kind, cur_q = sb["r"].data_ptr(), 1, sp[2]
+                    # (the fp32 frozen schedule: running = 0, automatic gather schedule)
+                    stage_fused_forward(cur_ptr, cur_kind, cur_q, Nb, sb, p, a + [bits, float(p["acts"][2].momentum), 0],
+                                        N_.aligned_workspace(B["ws32"]), stream)
+                    cur_ptr, cur_kind = sb["r"].data_ptr(), 1
+                cur_q = a[8]
         last = B["stages"][-1]
         return (last["r8"] if last["codes"] else last["r"]), cur_q, last
 
@@ -436,13 +406,7 @@ class FrozenHotPath:
 
     def __call__(self, x):
         """The Sequential's output tensor (NCHW, up-sampled, fake-quantised), like FusedHotPath.__call__."""
-        from .. import _native as N_
-        r, rq, last = self.forward_nhwc(x)
-        B = self._bufs
-        rc = N_.lib().cdn_codenet_unpack_nchw(r.data_ptr(), rq, B["out"].data_ptr(), x.shape[0], last["Co"], last["H"],
-                                              last["W"], 1, torch.cuda.current_stream(x.device).cuda_stream)
-        N_.check(rc, "cdn_codenet_unpack_nchw")
-        return B["out"]
+        return unpack_nchw(*self.forward_nhwc(x), self._bufs["out"])
 
     def overflowed(self):
         """True when some code saturated since the last call of this method (synchronises; resets the flag): the
@@ -461,17 +425,7 @@ class FrozenHotPath:
             run = lambda t: self.forward_codes(t, x_qstate, hw)[0]      # noqa: E731
         else:
             run = (lambda t: self.forward_codes(t)[0]) if codes_only else self.__call__
-        run(x)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            out = run(x)
-        self._graph = g
-
-        def replay():
-            g.replay()
-            return out
-        return replay
+        return capture_graph(run, x)
 
 
 class FrozenBackbone:

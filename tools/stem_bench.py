@@ -12,10 +12,11 @@ from codenet_amd import _native as N_
 m = model
 q0, act0 = m.layer0[0], m.layer0[1][1]
 w0, b0 = fb._folded(q0)
+ctx = fb._prepare(dev)
 out = torch.empty(64, 128 * 128, 24, device=dev)
 def run():
     rc = N_.lib().cdn_codenet_stem_forward(x.data_ptr(), 64, 512, 512, 24, 4, w0.reshape(24, 27).data_ptr(), b0.data_ptr(), 1,
-        *fb._act_args(act0, dev), fb._ws_ptr, fb._ws_bytes, out.data_ptr(), fb._stream)
+        *fb._act_args(act0, dev), ctx.ws_ptr, ctx.ws_bytes, out.data_ptr(), ctx.stream)
     N_.check(rc, "stem")
 for _ in range(3): run()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
