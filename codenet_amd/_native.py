@@ -152,6 +152,9 @@ _SIGNATURES = {
     "cdn_ctdet_decode_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
     "cdn_ctdet_flip_merge": (_i, [_vp, _vp] + [_i64] * 5 + [_vp, _vp, _vp]),
     "cdn_ctdet_decode": (_i, [_vp] * 3 + [_i64] * 4 + [_i, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "cdn_soft_nms_host": (_i, [_vp, _i64, _f, _f, _f, _i, _vp]),
+    "cdn_ctdet_merge_scales_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
+    "cdn_ctdet_merge_scales": (_i, [_vp, _vp] + [_i64] * 4 + [_i, _i, _f, _f, _f, _i] + [_vp] * 6),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

@@ -5,6 +5,7 @@ reference's helpers with the same names and argument meaning:
     transform_preds                  lib/utils/image.py:14-19,22-55 (rot = 0: closed form, no cv2)
     ctdet_post_process               lib/utils/post_process.py:86-103
     post_process / merge_outputs     lib/detectors/ctdet.py:48-72
+    soft_nms                         lib/models/external/nms.pyx:77-170 (multi-scale test / --nms)
     convert_eval_format / save_results   lib/datasets/dataset/pascal.py:58-79   (results.json for tools/reval.py)
     export_w4                        packed 4-bit weight codes + per-channel scales + QuantAct ranges of a
                                      quantised model (what an integer-only deployment of the W4A8 model loads)
@@ -112,13 +113,34 @@ def post_process(dets, meta, num_classes, scale=1):
     return dets[0]
 
 
+def soft_nms(boxes, sigma=0.5, Nt=0.3, threshold=0.001, method=0):
+    """lib/models/external/nms.pyx:77-170 with the reference's signature: IN PLACE on a float32 [N, 5] array
+    (x1, y1, x2, y2, score), returns keep = list(range(N_final)).  method 0 hard, 1 linear, 2 gaussian.  Runs on the
+    library's host routine (cdn_soft_nms_host: the arithmetic the GPU merge kernel uses, no GPU involved) and leaves the
+    whole array as the reference leaves it, INCLUDING the stale rows behind N_final that merge_outputs keeps."""
+    import ctypes
+    from . import _native as N_
+    if not (isinstance(boxes, np.ndarray) and boxes.dtype == np.float32 and boxes.ndim == 2 and boxes.shape[1] == 5):
+        raise ValueError("soft_nms needs a float32 [N, 5] array")           # (the reference: Cython buffer type error)
+    work = boxes if boxes.flags["C_CONTIGUOUS"] else np.ascontiguousarray(boxes)
+    n_keep = ctypes.c_int64(0)
+    rc = N_.lib().cdn_soft_nms_host(work.ctypes.data, work.shape[0], sigma, Nt, threshold, int(method),
+                                    ctypes.addressof(n_keep))
+    N_.check(rc, "cdn_soft_nms_host")
+    if work is not boxes:
+        boxes[...] = work
+    return list(range(n_keep.value))
+
+
 def merge_outputs(detections, num_classes, max_per_image=100, nms=False):
-    """CtdetDetector.merge_outputs for a single test scale (soft-NMS, used only with multi-scale testing or
-    --nms, is outside this port)."""
-    if nms or len(detections) > 1:
-        raise NotImplementedError("soft-NMS (multi-scale test / --nms) is not part of this port")
-    results = {j: np.concatenate([d[j] for d in detections], axis=0).astype(np.float32)
-               for j in range(1, num_classes + 1)}
+    """CtdetDetector.merge_outputs (ctdet.py:59-74): per class the detections of every test scale concatenated, with more
+    than one scale or --nms soft_nms(Nt=0.5, method=2) on them -- whose `keep` the reference ignores: the rows soft_nms
+    left behind its final N stay and take part in the cut -- then the max_per_image cut over all classes."""
+    results = {}
+    for j in range(1, num_classes + 1):
+        results[j] = np.concatenate([d[j] for d in detections], axis=0).astype(np.float32)
+        if len(detections) > 1 or nms:
+            soft_nms(results[j], Nt=0.5, method=2)
     scores = np.hstack([results[j][:, 4] for j in range(1, num_classes + 1)])
     if len(scores) > max_per_image:
         kth = len(scores) - max_per_image

@@ -6,7 +6,8 @@ restatement for CPU tensors and ``ctdet_decode_native`` on the HIP kernels) and 
 kernels; ``enable_fused()`` runs the WHOLE network on them -- backbone (pipeline.FusedBackbone), stages
 (pipeline.FusedHotPath), heads (pipeline.FusedHeads) -- and ``enable_fused(frozen_codes=True)`` the byte-code serving
 schedule (pipeline.FrozenBackbone / FrozenHotPath / FusedHeads.forward_codes); ``capture_process`` records network +
-decode as one HIP graph.
+decode as one HIP graph; ``process_scales`` / ``capture_process_scales`` run the S test scales of a multi-scale test as one
+batch and merge them on the GPU (``merge_scales_native``: post_process + soft-NMS + the max_per_image cut).
 """
 import hashlib
 
@@ -333,6 +334,7 @@ class ProcessBuffers:
     def __init__(self):
         self.sigmoid = {}
         self.decode_ws = {}
+        self.merge_ws = {}
 
     def sigmoid_buffer(self, hm, tag="hm"):
         # `tag` keeps the merged hm and wh of a flip test apart: a 2-class model gives both the shape [1,2,H,W]
@@ -350,6 +352,15 @@ class ProcessBuffers:
         return self.decode_ws[key]
 
 
+    def merge_block(self, device, need, stream, tag="results"):
+        # the result block of cdn_ctdet_merge_scales (boxes, row counts, thresholds back to back: one copy fetches all)
+        # and, tag "meta", the device copy of the crop parameters
+        key = (tag, device, need, stream.cuda_stream)
+        if key not in self.merge_ws:
+            self.merge_ws[key] = torch.zeros(need // 8 + 1, dtype=torch.float64, device=device)
+        return self.merge_ws[key]
+
+
 class _BoundedBuffers(ProcessBuffers):
     """Owner-less calls of ctdet_decode_native: at most `cap` workspaces are kept (oldest dropped first).  A captured
     graph keeps the raw workspace pointer, so an owner-less call under stream capture is refused: capture with an
@@ -364,6 +375,14 @@ class _BoundedBuffers(ProcessBuffers):
         while len(self.decode_ws) > self.cap:
             self.decode_ws.pop(next(iter(self.decode_ws)))
         return ws
+
+    def merge_block(self, device, need, stream, tag="results"):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("merge_scales_native under graph capture needs bufs=ProcessBuffers() owned by the capture")
+        blk = super().merge_block(device, need, stream, tag)
+        while len(self.merge_ws) > 2 * self.cap:
+            self.merge_ws.pop(next(iter(self.merge_ws)))
+        return blk
 
 
 _default_bufs = _BoundedBuffers()
@@ -479,6 +498,175 @@ def capture_process(model, images, reg_offset=True, cat_spec_wh=False, K=100, fl
         graph.replay()
         return result
     replay.buffers = bufs
+    return replay
+
+
+# ---- multi-scale test / --nms (test.py --test_scales / --nms; lib/detectors/base_detector.py:84-130, ctdet.py:48-74) ----
+
+def scale_metas(metas, scales):
+    """[B][S] meta dicts of pre_process ({'c', 's', 'out_height', 'out_width'}; a flat list of S dicts = one image) and
+    the S test scales -> float64 tensor [B, S, 6] = {c_x, c_y, s, out_w, out_h, scale}, the layout cdn_ctdet_merge_scales
+    reads."""
+    if metas and isinstance(metas[0], dict):
+        metas = [metas]
+    rows = [[[float(m["c"][0]), float(m["c"][1]), float(m["s"]), float(m["out_width"]), float(m["out_height"]),
+              float(sc)] for m, sc in zip(per_image, scales)] for per_image in metas]
+    t = torch.tensor(rows, dtype=torch.float64)
+    assert t.dim() == 3 and t.shape[1] == len(scales), "one meta per (image, scale)"
+    return t
+
+
+def unpack_merged(block, B, num_classes, R):
+    """The result block of cdn_ctdet_merge_scales as a HOST tensor -> per image {class 1 .. num_classes: float32 [n, 5]}
+    (what evalio.merge_outputs returns), plus the raw counters."""
+    import numpy as np
+    raw = block.numpy().view(np.uint8)
+    r256 = lambda n: (n + 255) // 256 * 256
+    nb, nc = r256(B * num_classes * R * 20), r256(B * num_classes * 4)
+    boxes = raw[:B * num_classes * R * 20].view(np.float32).reshape(B, num_classes, R, 5)
+    rows_out, rows_in, live = (raw[nb + i * nc: nb + i * nc + B * num_classes * 4].view(np.int32).reshape(B, num_classes)
+                               for i in range(3))
+    thresh = raw[nb + 3 * nc: nb + 3 * nc + B * 4].view(np.float32)
+    results = [{j + 1: boxes[b, j, :rows_out[b, j]].copy() for j in range(num_classes)} for b in range(B)]
+    return results, {"rows_out": rows_out, "rows_in": rows_in, "live": live, "thresh": thresh}
+
+
+def merge_scales_native(dets, metas, scales, num_classes, max_per_image=100, nms=None, bufs=None, raw=False,
+                        sigma=0.5, Nt=0.5, threshold=0.001, method=2):
+    """CtdetDetector.post_process of every test scale + merge_outputs on the GPU (codenet_merge.hip,
+    cdn_ctdet_merge_scales): dets [B, S, K, 6] (or [S, K, 6]: one image) float32 GPU detections as ctdet_decode_native
+    writes them, metas [B][S] dicts of pre_process (or the float64 [B, S, 6] tensor of scale_metas, on the GPU for a
+    captured graph), scales the S test scales.  nms None = the reference's rule `len(scales) > 1 or opt.nms` with
+    opt.nms False.  Returns a list with one {class: float32 [n, 5]} dict per image after ONE device-to-host copy;
+    raw=True returns the device tensors (block, boxes, rows_out, rows_in, live, thresh) and copies nothing.  The
+    defaults of sigma / Nt / threshold / method are merge_outputs' call soft_nms(results[j], Nt=0.5, method=2)."""
+    from . import _native as N_
+    if not (dets.is_cuda and dets.dtype == torch.float32):
+        raise NotImplementedError("merge_scales_native needs float32 GPU detections")
+    if dets.dim() == 3:
+        dets = dets.unsqueeze(0)
+    dets = dets.contiguous()
+    B, S, K, six = dets.shape
+    assert six == 6 and S == len(scales), "dets [B, S, K, 6] with one entry per test scale"
+    if nms is None:
+        nms = S > 1
+    lib = N_.lib()
+    owner = bufs if bufs is not None else _default_bufs
+    stream = torch.cuda.current_stream(dets.device)
+    if isinstance(metas, torch.Tensor):
+        meta = metas
+        if not meta.is_cuda:
+            dev_meta = owner.merge_block(dets.device, B * S * 48, stream, "meta")
+            dev_meta[:B * S * 6].copy_(meta.reshape(-1))
+            meta = dev_meta
+    else:
+        dev_meta = owner.merge_block(dets.device, B * S * 48, stream, "meta")
+        dev_meta[:B * S * 6].copy_(scale_metas(metas, scales).reshape(-1))
+        meta = dev_meta
+    assert meta.dtype == torch.float64 and meta.numel() >= B * S * 6 and meta.is_contiguous()
+    R = S * K
+    need = lib.cdn_ctdet_merge_scales_workspace_bytes(B, S, K, num_classes)
+    block = owner.merge_block(dets.device, need, stream)
+    r256 = lambda n: (n + 255) // 256 * 256
+    nb, nc = r256(B * num_classes * R * 20), r256(B * num_classes * 4)
+    p0 = block.data_ptr()
+    rc = lib.cdn_ctdet_merge_scales(dets.data_ptr(), meta.data_ptr(), B, S, K, num_classes, int(max_per_image),
+                                    int(bool(nms)), sigma, Nt, threshold, int(method), p0, p0 + nb, p0 + nb + nc,
+                                    p0 + nb + 2 * nc, p0 + nb + 3 * nc, stream.cuda_stream)
+    N_.check(rc, "cdn_ctdet_merge_scales")
+    if raw:
+        u8 = block.view(torch.uint8)
+        ints = [u8[nb + i * nc: nb + i * nc + B * num_classes * 4].view(torch.int32).view(B, num_classes) for i in range(3)]
+        return (block, u8[:B * num_classes * R * 20].view(torch.float32).view(B, num_classes, R, 5), ints[0], ints[1],
+                ints[2], u8[nb + 3 * nc: nb + 3 * nc + B * 4].view(torch.float32))
+    return unpack_merged(block.cpu(), B, num_classes, R)[0]
+
+
+def process_scales(model, images, n_scales, flip_test, metas, scales, num_classes=20, reg_offset=True, K=100,
+                   max_per_image=100, nms=None, bufs=None, raw=False, batched=False):
+    """One image at n_scales test scales (fix_res, the ctdet / pascal default, warps every scale onto the same
+    input_h x input_w crop): images [S, 3, R, R], with flip_test [2S, 3, R, R] = the S images followed by their S
+    W-mirrors.  Network -> (flip_test: sigmoid + mirror merge of the S pairs, cdn_ctdet_flip_merge with P = S) -> native
+    decode of the S maps -> merge_scales_native.  Returns (output dict, dets [S, K, 6], results) with results = the
+    {class: [n, 5]} dict of CtdetDetector.run (raw=True: the device tensors of merge_scales_native).  GPU tensors only.
+
+    batched=False (default, reference-faithful): the NETWORK runs once per scale, on [image] or [image, mirror] -- the
+    batches the reference's loop over the scales gives it -- and everything behind it on all scales at once.  Bit for
+    bit what S ``process`` calls + evalio.post_process + evalio.merge_outputs give, for every model: a QuantAct with
+    running ranges takes its statistics from the batch it sees and updates them once per call, and even an fp32 model is
+    not bitwise batch-invariant (measured: MIOpen's convolutions and the fused pointwise kernels, whose channel chunk
+    follows the batch size, sum in another order at batch 2S than at batch 2: logits move by ~1e-6).
+    batched=True: the S (2S) images as ONE network batch -- one pass instead of S; equal to the above up to those
+    last-bit / batch-statistics differences, and exactly equal to a batched network run merged on the host."""
+    from . import _native as N_
+    S = int(n_scales)
+    assert images.is_cuda and images.shape[0] == (2 * S if flip_test else S) and len(scales) == S
+    if bufs is None and isinstance(model, nn.Module):
+        bufs = model.__dict__.setdefault("_process_bufs", ProcessBuffers())
+    with torch.no_grad():
+        if batched:
+            output = model(images)[-1]
+        else:
+            outs = []
+            for s in range(S):
+                one = torch.cat([images[s:s + 1], images[S + s:S + s + 1]], 0) if flip_test else images[s:s + 1]
+                outs.append({k: v.clone() for k, v in model(one.contiguous())[-1].items()})     # (static buffers)
+            output = {k: torch.cat([o[k][0:1] for o in outs] + ([o[k][1:2] for o in outs] if flip_test else []), 0)
+                      for k in outs[0]}
+        reg = output["reg"] if reg_offset else None
+        static = bufs is not None and getattr(model, "_fused", False)
+        if flip_test:
+            hm2, wh2 = output["hm"].contiguous(), output["wh"].contiguous()
+            hm = bufs.sigmoid_buffer(hm2[0:S], "hm") if static else torch.empty_like(hm2[0:S])
+            wh = bufs.sigmoid_buffer(wh2[0:S], "wh") if static else torch.empty_like(wh2[0:S])
+            rc = N_.lib().cdn_ctdet_flip_merge(hm2.data_ptr(), wh2.data_ptr(), S, hm2.shape[1], wh2.shape[1], hm2.shape[2],
+                                               hm2.shape[3], hm.data_ptr(), wh.data_ptr(),
+                                               torch.cuda.current_stream(hm2.device).cuda_stream)
+            N_.check(rc, "cdn_ctdet_flip_merge")
+            dets = ctdet_decode_native(hm, wh, reg=reg[0:S] if reg is not None else None, K=K, bufs=bufs)
+            if hm2.data_ptr() != output["hm"].data_ptr():
+                output = dict(output)
+                output["hm"] = hm2
+        else:
+            hm = output["hm"]
+            sig = bufs.sigmoid_buffer(hm) if static else torch.empty_like(hm)
+            dets = ctdet_decode_native(hm, output["wh"], reg=reg, K=K, apply_sigmoid=True, heat_out=sig, bufs=bufs)
+            output = dict(output)
+            output["hm"] = sig
+        results = merge_scales_native(dets.view(1, S, K, 6), metas, scales, num_classes, max_per_image=max_per_image,
+                                      nms=nms, bufs=bufs, raw=raw)
+    return output, dets, (results if raw else results[0])
+
+
+def capture_process_scales(model, images, n_scales, flip_test, metas, scales, num_classes=20, reg_offset=True, K=100,
+                           max_per_image=100, nms=None, batched=False):
+    """``process_scales`` over the static `images` buffer as ONE HIP graph.  Returns replay() -> (output dict, dets,
+    results) where results is read back from the graph's result block by one copy per replay; replay.meta is the
+    float64 [1, S, 6] device tensor of crop parameters the graph reads (scale_metas layout): copy the next image's
+    values into it, and its S (2S) pre-processed scales into `images`, before each replay."""
+    assert getattr(model, "_fused", False) and images.is_cuda
+    S = int(n_scales)
+    bufs = ProcessBuffers()
+    meta = scale_metas(metas, scales).to(images.device)
+    kw = dict(num_classes=num_classes, reg_offset=reg_offset, K=K, max_per_image=max_per_image, nms=nms, bufs=bufs,
+              raw=True, batched=batched)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            process_scales(model, images, S, flip_test, meta, scales, **kw)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        output, dets, rawres = process_scales(model, images, S, flip_test, meta, scales, **kw)
+
+    def replay():
+        graph.replay()
+        return output, dets, unpack_merged(rawres[0].cpu(), 1, num_classes, S * K)[0][0]
+    replay.buffers = bufs
+    replay.meta = meta
+    replay.raw = rawres
     return replay
 
 

@@ -895,6 +895,54 @@ int cdn_ctdet_flip_merge(float *hm, const float *wh, int64_t P, int64_t cat, int
                          float *hm_out, float *wh_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-scale test / --nms (test.py --test_scales a,b,c / --nms): what CtdetDetector.run does behind ctdet_decode --
+ * post_process (lib/detectors/ctdet.py:48-57, lib/utils/post_process.py:86-103), the per-class merge across scales,
+ * soft_nms (lib/models/external/nms.pyx:77-170) and the max_per_image cut (ctdet.py:59-74).
+ *
+ * soft_nms, all three methods (0 hard, 1 linear, 2 gaussian), with the arithmetic widths of the C code Cython makes
+ * of nms.pyx (every `+ 1` is a DOUBLE addition, products of box sides are double, the gaussian calls the double exp;
+ * the table is in codenet_merge.hip and DESIGN.md).  Argmax with strict <: the lowest index wins among equal scores.
+ * REFERENCE-FAITHFUL TAIL: the reference discards a row by overwriting it with row N-1 and decrementing N; the slot
+ * beyond the new N is not cleared, and merge_outputs ignores the returned `keep`, so the stale rows [N, n) stay in
+ * the per-class arrays and take part in the max_per_image cut.  Both entry points reproduce the whole array the
+ * reference leaves: a row that was pulled leaves its old slot with its pre-decay score, a row discarded in place
+ * (position == N-1) keeps its decayed score.
+ *
+ * cdn_soft_nms_host: on the CPU, no HIP call; boxes [n][5] = x1, y1, x2, y2, score, HOST memory, in place;
+ *   *n_keep (may be NULL) = the final N = len(keep).  method outside 0..2, sigma == 0 with method 2: CDN_ERR_ARG.
+ *
+ * cdn_ctdet_merge_scales: one launch, one workgroup per image, capturable.
+ *   dets [B][S][K][6]   as cdn_ctdet_decode writes them for the S test scales of B images (output-map pixels)
+ *   meta [B][S][6]      DEVICE doubles {c_x, c_y, s, out_w, out_h, scale}: the crop of pre_process and the test scale
+ *   per image:  1. x = float32((p - out_w/2) * (s/out_w) + c_x) / float32(scale)   (y with out_h/2 and c_y; double
+ *                  inside, then a float32 division: evalio.transform_preds / post_process)
+ *               2. STABLE partition by class: inside a class rows are ordered by scale, then decode rank (the order
+ *                  np.concatenate gives the reference; it decides ties and the tail layout).  Rows whose class is
+ *                  not an integer in [0, num_classes) are dropped, as on the host.
+ *               3. do_nms != 0: soft_nms(sigma, Nt, threshold, method) per class
+ *               4. more than max_per_image rows (tails included): thresh = the max_per_image-th largest score of
+ *                  all rows, rows with score >= thresh survive in order (ties may keep more, as np.partition does)
+ *   boxes    [B][num_classes][S*K][5]  the surviving rows of every class, compacted to the front (the rest of a
+ *                                      class's S*K slots is not written)
+ *   rows_out, rows_in, live  int32 [B][num_classes]: surviving rows, rows of the class before soft-NMS, the
+ *                                      soft-NMS N (= rows_in without do_nms)
+ *   thresh   [B]                       the cut's threshold, -inf when the image had at most max_per_image rows
+ * Capacity: S*K <= 4096 rows per image, K <= 1024, num_classes <= 256 (CDN_ERR_UNSUPPORTED beyond).  LDS per
+ * workgroup: 20 B per row (the class lists: every row is in at most one) + 4 B per row (pre-decay scores) + 16 waves x
+ * 64 ballot words of 8 B = 24 * S*K + 8192 bytes, 106496 of the 160 KiB at capacity.
+ * The kernel needs no global scratch.  cdn_ctdet_merge_scales_workspace_bytes is the size of ONE block that holds
+ * the five results back to back, each section rounded up to 256 bytes, in the order boxes, rows_out, rows_in, live,
+ * thresh: a caller that carves the result pointers out of such a block fetches everything with one copy.
+ * Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_soft_nms_host(float *boxes, int64_t n, float sigma, float Nt, float threshold, int method, int64_t *n_keep);
+size_t cdn_ctdet_merge_scales_workspace_bytes(int64_t B, int64_t S, int64_t K, int64_t num_classes);
+int cdn_ctdet_merge_scales(const float *dets, const double *meta, int64_t B, int64_t S, int64_t K, int64_t num_classes,
+                           int max_per_image, int do_nms, float sigma, float Nt, float threshold, int method,
+                           float *boxes, int32_t *rows_out, int32_t *rows_in, int32_t *live, float *thresh,
+                           void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

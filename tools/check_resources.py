@@ -53,6 +53,9 @@ SGPR_SPILLS_OK_X = 32      # (SGPR spills go to VGPR lanes: tolerated in the ker
 BUDGET_FROZEN = {"pwq8_kernelILi64ELi64E": 64, "dwpwq8_kernelILi1ELi4ELi2ELi128E": 168, "dwpwq8_kernelILi1ELi4ELi1ELi64E": 168,
                  "dwpwq8_kernelILi2ELi2ELi1ELi64E": 168, "dwpwq8_kernelILi2ELi2ELi2ELi128E": 168,
                  "dwpwq8_kernelILi1ELi4ELi2ELi256ELi32E": 256, "dwpwq8_kernelILi2ELi2ELi2ELi256ELi32E": 256}
+# codenet_merge.hip: one 1024-thread workgroup per image (four waves per SIMD: 128 VGPRs); its soft-NMS inner loop
+# carries double arithmetic and the double exp -- 74 VGPRs when it was written, no scratch
+BUDGET_MERGE = {"merge_scales_kernel": 128}
 
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
@@ -87,7 +90,7 @@ def check():
                 problems.append("%s uses %d VGPRs (budget %d)" % (n, r["vgpr"], cap))
     res.update(res_l)
     for src, extra, budget in (("codenet_stage.hip", ("-fno-slp-vectorize",), BUDGET_STAGE), ("dcn_generic.hip", (), BUDGET_GENERIC),
-                               ("codenet_frozen.hip", (), BUDGET_FROZEN)):
+                               ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -114,7 +117,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))

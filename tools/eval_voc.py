@@ -16,7 +16,7 @@ cv2 is not available here: images are read with PIL and the affine crop is done 
 (cv2.INTER_LINEAR's arithmetic differs in the last bits; this is stated in the output).
 
     python tools/eval_voc.py --data /data --load_model exp/ctdet/pascal_shufflenetv2_config_c/model_last.pth \
-        --res 512 --quantize [--w2] [--maxpool] [--flip_test] [--reference-json results_ref.json]
+        --res 512 --quantize [--w2] [--maxpool] [--flip_test] [--test_scales 0.5,0.75,1,1.25,1.5] [--nms]
 """
 import argparse
 import json
@@ -35,14 +35,20 @@ MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32)                        
 STD = np.array([0.229, 0.224, 0.225], dtype=np.float32)
 
 
-def pre_process(img, res):
+def pre_process(img, res, scale=1.0):
     """BaseDetector.pre_process with fix_res (ctdet on pascal: opts.py keep_res False): c = image centre,
     s = max(h, w); the un-rotated affine map of get_affine_transform (lib/utils/image.py:30-55) sends the square of
-    side s around c onto the res x res input.  img: uint8 [H, W, 3] RGB -> ([1,3,res,res] float32, meta)."""
+    side s around c onto the res x res input.  img: uint8 [H, W, 3] RGB -> ([1,3,res,res] float32, meta).
+    scale (--test_scales, base_detector.py:47-55): the image is first resized to int(h * scale) x int(w * scale), c is
+    the centre of the RESIZED image and s stays max(h, w) of the unscaled one, so every scale lands on the same
+    res x res crop (post_process divides the boxes by scale again)."""
     h, w = img.shape[:2]
-    c = np.array([w / 2.0, h / 2.0], dtype=np.float32)
-    s = float(max(h, w))
     t = torch.from_numpy(np.ascontiguousarray(img).copy()).permute(2, 0, 1).float().unsqueeze(0)
+    s = float(max(h, w))
+    if scale != 1.0:
+        h, w = int(h * scale), int(w * scale)
+        t = torch.nn.functional.interpolate(t, size=(h, w), mode="bilinear", align_corners=False)   # (cv2.resize)
+    c = np.array([w / 2.0, h / 2.0], dtype=np.float32)
     # output pixel (u, v) <- source (c + ((u, v) - res/2) * s/res); grid_sample wants normalised source coordinates
     u = (torch.arange(res, dtype=torch.float32) - res / 2.0) * (s / res)
     xs, ys = c[0] + u, c[1] + u
@@ -133,8 +139,30 @@ def run_voc(args):
     results = {}
     ids = sorted(images)[: args.limit or None]
     static, replay = None, None        # the network + [flip merge +] decode as ONE HIP graph over a static input buffer
+    scales = [float(v) for v in str(getattr(args, "test_scales", "1")).split(",")]
+    multi = len(scales) > 1 or bool(getattr(args, "nms", False))   # all scales of an image in one graph, merged on the GPU
     for n, img_id in enumerate(ids):
         img = np.asarray(Image.open(os.path.join(root, "images", images[img_id]["file_name"])).convert("RGB"))
+        if multi:
+            pre = [pre_process(img, args.res, sc) for sc in scales]
+            inp = torch.cat([p[0] for p in pre], 0)
+            metas = [p[1] for p in pre]
+            if args.flip_test:
+                inp = torch.cat([inp, torch.flip(inp, [3])], 0)
+            if static is None:
+                static = inp.cuda()
+                ranges = [(b, b.clone()) for nme, b in model.named_buffers() if nme.endswith(("x_min", "x_max"))]
+                replay = harness.capture_process_scales(model, static, len(scales), args.flip_test, metas, scales,
+                                                        nms=True, batched=bool(getattr(args, "batch_scales", False)))
+                with torch.no_grad():
+                    for b, saved in ranges:
+                        b.copy_(saved)
+            static.copy_(inp, non_blocking=True)
+            replay.meta.copy_(harness.scale_metas(metas, scales), non_blocking=True)
+            results[img_id] = replay()[2]
+            if n % 500 == 0:
+                print("%d / %d images" % (n, len(ids)), file=sys.stderr)
+            continue
         inp, meta = pre_process(img, args.res)
         if args.flip_test:
             inp = torch.cat([inp, torch.flip(inp, [3])], 0)
@@ -212,6 +240,11 @@ def main():
     ap.add_argument("--w2", action="store_true")
     ap.add_argument("--maxpool", action="store_true")
     ap.add_argument("--flip_test", action="store_true")
+    ap.add_argument("--test_scales", default="1", help="comma list of test scales (test.py --test_scales), e.g. "
+                    "0.5,0.75,1,1.25,1.5: the scales of an image run as one batch and are merged by soft-NMS on the GPU")
+    ap.add_argument("--nms", action="store_true", help="soft-NMS also with a single test scale (test.py --nms)")
+    ap.add_argument("--batch_scales", action="store_true", help="run the scales of an image as ONE network batch instead "
+                    "of one pass per scale (faster; QuantAct ranges then update once per image, not once per scale)")
     ap.add_argument("--limit", type=int, default=0)
     ap.add_argument("--out", default="gpurun_out/voc_eval")
     ap.add_argument("--proxy-images", type=int, default=0, help="without data / checkpoint: also run the detection-"
