@@ -43,7 +43,8 @@ class GraphedTrainStep:
         ``mean()`` / ``sum()`` (ATen's multi-block reduction: a semaphore word zeroed by a memset node), and another model
         takes its FIRST eager step between two replays -- that replay's reduction leaves its output unwritten while the
         gradients and parameters of the same replay are right (the backward of a mean does not read its value).  A
-        two-level reduction (``v.square().reshape(-1, 64).sum(1).sum() / v.numel()``: no semaphore) does not show it."""
+        two-level reduction (``v.square().reshape(-1, 64).sum(1).sum() / v.numel()``: no semaphore) does not show it, and neither does the native criterion
+        (``codenet_amd.losses.CtdetLoss``: its sums are fixed-order slabs of this library's own kernels)."""
 
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
         if not unvalidated and not self.is_stage_stack(net):

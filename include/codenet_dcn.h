@@ -943,6 +943,65 @@ int cdn_ctdet_merge_scales(const float *dets, const double *meta, int64_t B, int
                            void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The ctdet training criterion (main.py / quant_main.py: ModelWithLoss -> CtdetLoss, lib/trains/ctdet.py:17-74) and
+ * the target maps it is fed (lib/datasets/sample/ctdet.py:87-122).  codenet_loss.hip; Python: codenet_amd/losses.py.
+ *
+ * Covered: FocalLoss on hm behind _sigmoid (lib/models/losses.py:42-67, models/utils.py:9-11), RegL1Loss
+ * (reg_loss 0, --reg_loss l1) or RegLoss (reg_loss 1, sl1) on wh and reg (losses.py:100-155), num_stacks >= 1.
+ * wh == NULL / reg == NULL switch that term off (opt.wh_weight == 0; not opt.reg_offset or opt.off_weight == 0).
+ * Not covered (the Python mirror composes them from PyTorch): mse_loss, dense_wh, norm_wh, cat_spec_wh, eval_oracle_*.
+ *
+ *   hm [N][C][H][W] logits, hm_gt the same shape;  wh, reg [N][2][H][W];  wh_gt, reg_gt [N][M][2];
+ *   ind [N][M] int64 cells y * W + x;  reg_mask [N][M] uint8.   All contiguous float32 unless said otherwise.
+ * Per element, float32 in the reference's operation order: p = clamp(sigmoid(x), 1e-4, 1 - 1e-4);
+ *   gt == 1: log(p) (1-p)^2 and num_pos += 1;   gt < 1: log(1-p) p^2 (1-gt)^4;
+ *   per (row, channel): |pred m - target m| (l1) or its smooth-L1 form, pred = head[b][c][ind[b][k]], m = reg_mask.
+ * SUMS: per thread in double, a fixed tree per wave and workgroup, one slab of partials per workgroup, added in index
+ * order by a one-workgroup finish: no floating-point atomics, so a call is a pure function of its inputs bit for bit.
+ * The finish rounds the sums to float32 and applies the reference's scalar arithmetic: `- neg` when num_pos == 0, else
+ * `- (pos + neg) / num_pos`; RegL1Loss divides by the sum of the EXPANDED mask + 1e-4 (2 x the row sum), RegLoss by
+ * the row sum + 1e-4; every term `/ num_stacks`; loss = hm_weight hm + wh_weight wh + off_weight off.
+ * A cell outside [0, H*W) is never dereferenced: forward turns the term NaN, backward skips the row.
+ *
+ * cdn_ctdet_loss_forward: call once per stack (stack = 0 .. num_stacks-1, the same targets and workspace); the call
+ *   with stack == num_stacks-1 also runs the finish.  Two launches at most, no host synchronisation, capturable.
+ *   hm_sigmoid  NULL, or [N][C][H][W]: receives p (what the reference leaves in output['hm'])
+ *   result      8 floats: loss, hm_loss, wh_loss, off_loss, then what backward reads -- the hm denominator (num_pos,
+ *               or 1), the regression denominator, num_pos, the mask's row sum
+ *   workspace   cdn_ctdet_loss_workspace_bytes(...) bytes, 256-byte aligned, every word written before it is read
+ * cdn_ctdet_loss_backward: one launch per stack.  grad_result: 4 device floats, the gradient of (loss, hm_loss,
+ *   wh_loss, off_loss).  grad_hm is RECOMPUTED from logits and target (zero where the sigmoid is outside the clamp):
+ *   2 maps read + 1 written, the same traffic as reading a stored unscaled gradient and without its buffer.
+ *   grad_wh / grad_reg (NULL: not wanted) are dense [N][2][H][W]: the kernel clears them and writes the object cells;
+ *   rows that share a cell are added in row order by the first of them.
+ *
+ * cdn_ctdet_targets: one launch, one workgroup per (image, class) plane, no memset, no atomics.
+ *   boxes [N][M][4] x1, y1, x2, y2 in OUTPUT-map pixels after the affine map and the clip to [0, W-1] x [0, H-1];
+ *   classes [N][M] int32; counts [N] int32 rows in use (clamped to [0, M]).
+ *   A row takes part when h = y2 - y1 > 0 and w = x2 - x1 > 0 (float32) and 0 <= class < C:
+ *     radius = max(0, int(gaussian_radius(ceil(h), ceil(w)))) in double (lib/utils/image.py:90-110), sigma =
+ *     (2 r + 1) / 6, ct = ((x1 + x2) / 2, (y1 + y2) / 2) in float32, ct_int by truncation;
+ *     hm[b][class] = max(hm, float32(exp(-(dx^2 + dy^2) / (2 sigma^2)))) over the window |dx|, |dy| <= r, double exp;
+ *     wh = (w, h), reg = ct - ct_int, ind = ct_int.y * W + ct_int.x, reg_mask = 1.
+ *   Every other row, and every row at or beyond counts[b], is zero in wh, reg, ind and reg_mask.  M <= 2048.
+ * Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+size_t cdn_ctdet_loss_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int64_t M, int num_stacks);
+int cdn_ctdet_loss_forward(const float *hm, const float *wh, const float *reg, const float *hm_gt, const float *wh_gt,
+                           const float *reg_gt, const int64_t *ind, const uint8_t *reg_mask, int64_t N, int64_t C,
+                           int64_t H, int64_t W, int64_t M, int stack, int num_stacks, int reg_loss, float hm_weight,
+                           float wh_weight, float off_weight, float *hm_sigmoid, float *result, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int cdn_ctdet_loss_backward(const float *hm, const float *wh, const float *reg, const float *hm_gt, const float *wh_gt,
+                            const float *reg_gt, const int64_t *ind, const uint8_t *reg_mask, int64_t N, int64_t C,
+                            int64_t H, int64_t W, int64_t M, int num_stacks, int reg_loss, float hm_weight,
+                            float wh_weight, float off_weight, const float *result, const float *grad_result,
+                            float *grad_hm, float *grad_wh, float *grad_reg, void *stream);
+int cdn_ctdet_targets(const float *boxes, const int32_t *classes, const int32_t *counts, int64_t N, int64_t M, int64_t C,
+                      int64_t H, int64_t W, float *hm, float *wh, float *reg, int64_t *ind, uint8_t *reg_mask,
+                      void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

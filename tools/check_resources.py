@@ -56,6 +56,10 @@ BUDGET_FROZEN = {"pwq8_kernelILi64ELi64E": 64, "dwpwq8_kernelILi1ELi4ELi2ELi128E
 # codenet_merge.hip: one 1024-thread workgroup per image (four waves per SIMD: 128 VGPRs); its soft-NMS inner loop
 # carries double arithmetic and the double exp -- 74 VGPRs when it was written, no scratch
 BUDGET_MERGE = {"merge_scales_kernel": 128}
+# codenet_loss.hip: streaming kernels in 256-thread workgroups that hide HBM latency with occupancy -- eight waves per
+# SIMD (64 VGPRs) for the two heat-map passes and the finish; the target kernel carries the double exp (four waves)
+BUDGET_LOSS = {"ctdet_loss_fwd_kernel": 64, "ctdet_loss_bwd_kernel": 64, "ctdet_loss_finish_kernel": 64,
+               "ctdet_targets_kernel": 128}
 
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
@@ -90,7 +94,8 @@ def check():
                 problems.append("%s uses %d VGPRs (budget %d)" % (n, r["vgpr"], cap))
     res.update(res_l)
     for src, extra, budget in (("codenet_stage.hip", ("-fno-slp-vectorize",), BUDGET_STAGE), ("dcn_generic.hip", (), BUDGET_GENERIC),
-                               ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE)):
+                               ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE),
+                               ("codenet_loss.hip", (), BUDGET_LOSS)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -117,7 +122,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))
