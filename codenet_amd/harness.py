@@ -471,12 +471,14 @@ def process(model, images, flip_test=True, reg_offset=True, cat_spec_wh=False, K
     return output, dets
 
 
-def capture_process(model, images, reg_offset=True, cat_spec_wh=False, K=100, flip_test=False):
+def capture_process(model, images, reg_offset=True, cat_spec_wh=False, K=100, flip_test=False, pre=None):
     """Capture ``process(model, images, flip_test)`` -- the whole fused network + native decode (flip_test: images =
     [image, its W-mirror] and the native sigmoid + mirror merge in between, the README's test procedure) -- over the
     static `images` buffer into one HIP graph (about 110 kernel launches; at small batches the Python /
     launch overhead of issuing them one by one dominates).  Returns replay() -> (output dict, dets); copy
-    new images into `images` before each replay.  Needs model.enable_fused() and a GPU tensor."""
+    new images into `images` before each replay.  Needs model.enable_fused() and a GPU tensor.
+    pre (a preproc.PreProcess that has an image loaded): ``pre.run(images)`` becomes the first node of the graph, so a
+    replay needs only ``pre.load(next image)`` -- the image bytes and the crop table, not the float planes."""
     assert getattr(model, "_fused", False) and images.is_cuda
     bufs = ProcessBuffers()          # owned by this capture: kept alive by replay(), released with it
     kw = dict(flip_test=bool(flip_test), reg_offset=reg_offset, cat_spec_wh=cat_spec_wh, K=K, bufs=bufs)
@@ -484,6 +486,8 @@ def capture_process(model, images, reg_offset=True, cat_spec_wh=False, K=100, fl
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):                 # warm-up: buffers, cached weights, kernel attributes
         for _ in range(3):
+            if pre is not None:
+                pre.run(images)
             process(model, images, **kw)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
@@ -492,6 +496,8 @@ def capture_process(model, images, reg_offset=True, cat_spec_wh=False, K=100, fl
     # them again INSIDE the capture -- and the zero fill of the 84-MB decode workspace became a graph node, replayed
     # with every batch (12 us + a boundary in the kernel trace of round 4)
     with torch.cuda.graph(graph, stream=side):
+        if pre is not None:
+            pre.run(images)
         result = process(model, images, **kw)
 
     def replay():
@@ -639,11 +645,12 @@ def process_scales(model, images, n_scales, flip_test, metas, scales, num_classe
 
 
 def capture_process_scales(model, images, n_scales, flip_test, metas, scales, num_classes=20, reg_offset=True, K=100,
-                           max_per_image=100, nms=None, batched=False):
+                           max_per_image=100, nms=None, batched=False, pre=None):
     """``process_scales`` over the static `images` buffer as ONE HIP graph.  Returns replay() -> (output dict, dets,
     results) where results is read back from the graph's result block by one copy per replay; replay.meta is the
     float64 [1, S, 6] device tensor of crop parameters the graph reads (scale_metas layout): copy the next image's
-    values into it, and its S (2S) pre-processed scales into `images`, before each replay."""
+    values into it, and its S (2S) pre-processed scales into `images`, before each replay.  pre (a preproc.PreProcess
+    with an image loaded): ``pre.run(images)`` is the first node of the graph and fills `images` itself."""
     assert getattr(model, "_fused", False) and images.is_cuda
     S = int(n_scales)
     bufs = ProcessBuffers()
@@ -654,11 +661,15 @@ def capture_process_scales(model, images, n_scales, flip_test, metas, scales, nu
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         for _ in range(3):
+            if pre is not None:
+                pre.run(images)
             process_scales(model, images, S, flip_test, meta, scales, **kw)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph, stream=side):
+        if pre is not None:
+            pre.run(images)
         output, dets, rawres = process_scales(model, images, S, flip_test, meta, scales, **kw)
 
     def replay():

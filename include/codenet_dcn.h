@@ -943,6 +943,32 @@ int cdn_ctdet_merge_scales(const float *dets, const double *meta, int64_t B, int
                            void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image pre-processing: CtdetDetector.pre_process for every test scale of an image
+ * (lib/detectors/base_detector.py:47-77, fix_res) and the input crop of the training sample
+ * (lib/datasets/sample/ctdet.py:84-97) -- resize, affine crop with a zero border, optional source flip,
+ * (v / 255 - mean) / std, HWC uint8 -> float32 planes, the W-mirrors of --flip_test.  codenet_preproc.hip; Python:
+ * codenet_amd/preproc.py.  The arithmetic is an INTEGER specification of this project (DESIGN.md section 7.4b;
+ * tests/preproc_ref.py restates it in numpy and the kernel equals it bit for bit); it has the form of cv2.resize +
+ * cv2.warpAffine(INTER_LINEAR) on uint8 but makes no claim about cv2's own bits.
+ *
+ * cdn_ctdet_pre_process: one launch, capturable; the launch geometry depends on P, out_h, out_w and mirror only.
+ *   src_arena  DEVICE bytes that hold the source images: uint8, HWC, 3 channels, row pitch >= 3 w
+ *   items      DEVICE doubles [P][16] (integers are exact in a double, as in the meta of cdn_ctdet_merge_scales):
+ *                {src_off, h, w, pitch, new_h, new_w, ratio_y, ratio_x, flip_src, M0, M1, M2, M3, M4, M5, 0}
+ *              src_off / pitch in bytes; new_h x new_w the size after the resize (equal to h x w: no resize), ratio =
+ *              n_src / n_dst per axis, computed in double by the host; M maps output (x, y) to a position in the RESIZED
+ *              image: (M0 x + M1 y + M2, M3 x + M4 y + M5); flip_src != 0 reads the resized image W-mirrored.
+ *              The kernel trusts the table: the caller keeps every item inside the arena and |M . corner| < 2^20.
+ *   lut        DEVICE float32 [256][3]: lut[v][c] = float32((v / 255.0 - mean[c]) / std[c]) evaluated in double
+ *   out        float32 [P][3][out_h][out_w]; mirror != 0: [2P][3][out_h][out_w] and plane set P + i is the exact
+ *              W-mirror of plane set i (the reference's images[:, :, :, ::-1])
+ * A resized image with new_h == 0 or new_w == 0 has no pixel: the whole crop is border, lut[0].
+ * P <= 65535, out_h * out_w < 2^31 (CDN_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_ctdet_pre_process(const unsigned char *src_arena, const double *items, int64_t P, const float *lut, float *out,
+                          int64_t out_h, int64_t out_w, int mirror, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The ctdet training criterion (main.py / quant_main.py: ModelWithLoss -> CtdetLoss, lib/trains/ctdet.py:17-74) and
  * the target maps it is fed (lib/datasets/sample/ctdet.py:87-122).  codenet_loss.hip; Python: codenet_amd/losses.py.
  *

@@ -60,6 +60,9 @@ BUDGET_MERGE = {"merge_scales_kernel": 128}
 # SIMD (64 VGPRs) for the two heat-map passes and the finish; the target kernel carries the double exp (four waves)
 BUDGET_LOSS = {"ctdet_loss_fwd_kernel": 64, "ctdet_loss_bwd_kernel": 64, "ctdet_loss_finish_kernel": 64,
                "ctdet_targets_kernel": 128}
+# codenet_preproc.hip: one thread per output pixel, bound by its stores -- eight waves per SIMD (64 VGPRs; 52 when it was
+# written, with the double geometry and the recomputed resize taps), no scratch
+BUDGET_PREPROC = {"pre_process_kernel": 64}
 
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
@@ -95,7 +98,7 @@ def check():
     res.update(res_l)
     for src, extra, budget in (("codenet_stage.hip", ("-fno-slp-vectorize",), BUDGET_STAGE), ("dcn_generic.hip", (), BUDGET_GENERIC),
                                ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE),
-                               ("codenet_loss.hip", (), BUDGET_LOSS)):
+                               ("codenet_loss.hip", (), BUDGET_LOSS), ("codenet_preproc.hip", (), BUDGET_PREPROC)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -122,7 +125,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))

@@ -16,7 +16,11 @@ cv2 is not available here: images are read with PIL and the affine crop is done 
 (cv2.INTER_LINEAR's arithmetic differs in the last bits; this is stated in the output).
 
     python tools/eval_voc.py --data /data --load_model exp/ctdet/pascal_shufflenetv2_config_c/model_last.pth \
-        --res 512 --quantize [--w2] [--maxpool] [--flip_test] [--test_scales 0.5,0.75,1,1.25,1.5] [--nms]
+        --res 512 --quantize [--w2] [--maxpool] [--flip_test] [--test_scales 0.5,0.75,1,1.25,1.5] [--nms] [--gpu_pre]
+
+--gpu_pre: the image BYTES go to the device and codenet_amd.preproc (codenet_preproc.hip) builds every test scale and
+mirror there, as the first node of the captured graph -- an integer resize + crop of this project's own (DESIGN.md
+section 7.4b), within 10 grey levels of the float path above on noise, not a copy of cv2's bits either.
 """
 import argparse
 import json
@@ -27,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from codenet_amd import evalio, harness
+from codenet_amd import evalio, harness, preproc
 
 CLASSES = ["aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog",
            "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor"]   # pascal.py:32-36
@@ -141,12 +145,41 @@ def run_voc(args):
     static, replay = None, None        # the network + [flip merge +] decode as ONE HIP graph over a static input buffer
     scales = [float(v) for v in str(getattr(args, "test_scales", "1")).split(",")]
     multi = len(scales) > 1 or bool(getattr(args, "nms", False))   # all scales of an image in one graph, merged on the GPU
+    pre = None
+    if getattr(args, "gpu_pre", False):
+        # resize + crop + normalise + mirrors on the GPU, inside the graph: per image only the bytes and the crop table go
+        # up.  The arena holds the largest image of the annotation file (1024 x 1024 when it does not give the sizes)
+        pre = preproc.PreProcess(args.res, args.res, scales=scales if multi else (1.0,), flip_test=args.flip_test,
+                                 max_h=max(im.get("height", 0) for im in images.values()) or 1024,
+                                 max_w=max(im.get("width", 0) for im in images.values()) or 1024)
     for n, img_id in enumerate(ids):
         img = np.asarray(Image.open(os.path.join(root, "images", images[img_id]["file_name"])).convert("RGB"))
+        if pre is not None:
+            metas = pre.load(img)
+            if static is None:
+                static = torch.empty(pre.out_shape(), dtype=torch.float32, device="cuda")
+                ranges = [(b, b.clone()) for nme, b in model.named_buffers() if nme.endswith(("x_min", "x_max"))]
+                if multi:
+                    replay = harness.capture_process_scales(model, static, len(scales), args.flip_test, metas, scales, nms=True,
+                                                            batched=bool(getattr(args, "batch_scales", False)), pre=pre)
+                else:
+                    replay = harness.capture_process(model, static, flip_test=args.flip_test, pre=pre)
+                with torch.no_grad():
+                    for b, saved in ranges:
+                        b.copy_(saved)
+            if multi:
+                replay.meta.copy_(harness.scale_metas(metas, scales), non_blocking=True)
+                results[img_id] = replay()[2]
+            else:
+                dets = replay()[1].clone()
+                results[img_id] = evalio.merge_outputs([evalio.post_process(dets, metas[0], 20)], 20)
+            if n % 500 == 0:
+                print("%d / %d images" % (n, len(ids)), file=sys.stderr)
+            continue
         if multi:
-            pre = [pre_process(img, args.res, sc) for sc in scales]
-            inp = torch.cat([p[0] for p in pre], 0)
-            metas = [p[1] for p in pre]
+            per_scale = [pre_process(img, args.res, sc) for sc in scales]
+            inp = torch.cat([p[0] for p in per_scale], 0)
+            metas = [p[1] for p in per_scale]
             if args.flip_test:
                 inp = torch.cat([inp, torch.flip(inp, [3])], 0)
             if static is None:
@@ -190,7 +223,9 @@ def run_voc(args):
         aps.append(voc_eval(rows, gts[c]))
         print("AP for %s = %.4f" % (CLASSES[c - 1], aps[-1]))
     out = {"AP50": float(np.mean(aps)), "per_class": dict(zip(CLASSES, map(float, aps))), "images": len(ids),
-           "note": "VOC07 11-point, IoU 0.5; pre-processing by PIL + torch bilinear grid_sample (cv2 absent)"}
+           "note": "VOC07 11-point, IoU 0.5; pre-processing by PIL + " + (
+               "the integer resize / crop of codenet_preproc.hip on the GPU (--gpu_pre; cv2 absent)" if pre is not None
+               else "torch bilinear grid_sample (cv2 absent)")}
     if args.reference_ap50 is not None:
         out["delta_vs_reference"] = out["AP50"] - args.reference_ap50
     print(json.dumps(out))
@@ -245,6 +280,8 @@ def main():
     ap.add_argument("--nms", action="store_true", help="soft-NMS also with a single test scale (test.py --nms)")
     ap.add_argument("--batch_scales", action="store_true", help="run the scales of an image as ONE network batch instead "
                     "of one pass per scale (faster; QuantAct ranges then update once per image, not once per scale)")
+    ap.add_argument("--gpu_pre", action="store_true", help="pre-process on the GPU inside the captured graph "
+                    "(codenet_amd.preproc: integer resize + crop, DESIGN.md section 7.4b) instead of on the host")
     ap.add_argument("--limit", type=int, default=0)
     ap.add_argument("--out", default="gpurun_out/voc_eval")
     ap.add_argument("--proxy-images", type=int, default=0, help="without data / checkpoint: also run the detection-"
