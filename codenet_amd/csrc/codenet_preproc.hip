@@ -62,19 +62,11 @@ __device__ __forceinline__ Axis resize_axis(int d, int n_src, double ratio) {
 
 __device__ __forceinline__ long long fix10(double v) { return __double2ll_rn(v * 1024.0); }   // (x 2^10: exact)
 
-__global__ void __launch_bounds__(kThreads)
-pre_process_kernel(const unsigned char *__restrict__ arena, const double *__restrict__ items,
-                   const float *__restrict__ lut, float *__restrict__ out, int out_h, int out_w, int P, int mirror) {
+// The crop of one output pixel (x, y) of an item (`it`: its 16 doubles of the table): the three uint8 values of the resized,
+// cropped and optionally source-flipped image, 0 for the border.  Shared by pre_process_kernel and crop_sum_kernel.
+__device__ __forceinline__ void crop_pixel(const unsigned char *__restrict__ arena, const double *__restrict__ it, int x,
+                                           int y, int (&v)[3]) {
 #pragma clang fp contract(off)
-  __shared__ float s_lut[256 * 3];
-  for (int k = threadIdx.x; k < 256 * 3; k += kThreads) s_lut[k] = lut[k];
-  __syncthreads();
-  const int item = blockIdx.y;
-  const int hw = out_h * out_w;
-  const int pix = blockIdx.x * kThreads + threadIdx.x;
-  if (pix >= hw) return;
-  const int y = pix / out_w, x = pix - y * out_w;
-  const double *it = items + (size_t)item * kItem;
   const unsigned char *src = arena + (long long)it[0];
   const int h = (int)it[1], w = (int)it[2];
   const long long pitch = (long long)it[3];
@@ -123,15 +115,137 @@ pre_process_kernel(const unsigned char *__restrict__ arena, const double *__rest
       }
     }
   }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = (acc[c] + (1 << 14)) >> 15;
+}
+
+__global__ void __launch_bounds__(kThreads)
+pre_process_kernel(const unsigned char *__restrict__ arena, const double *__restrict__ items,
+                   const float *__restrict__ lut, float *__restrict__ out, int out_h, int out_w, int P, int mirror) {
+  __shared__ float s_lut[256 * 3];
+  for (int k = threadIdx.x; k < 256 * 3; k += kThreads) s_lut[k] = lut[k];
+  __syncthreads();
+  const int item = blockIdx.y;
+  const int hw = out_h * out_w;
+  const int pix = blockIdx.x * kThreads + threadIdx.x;
+  if (pix >= hw) return;
+  const int y = pix / out_w, x = pix - y * out_w;
+  int v[3];
+  crop_pixel(arena, items + (size_t)item * kItem, x, y, v);
   const size_t plane = (size_t)hw;
   float *o = out + (size_t)item * 3 * plane + pix;
   float *m = out + ((size_t)P + item) * 3 * plane + (size_t)y * out_w + (out_w - 1 - x);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int v = (acc[c] + (1 << 14)) >> 15;
-    const float f = s_lut[v * 3 + c];
+    const float f = s_lut[v[c] * 3 + c];
     o[c * plane] = f;
     if (mirror) m[c * plane] = f;
+  }
+}
+
+// ---- colour augmentation of the training sample (tests/color_aug_ref.py restates it) --------------
+// lib/datasets/sample/ctdet.py:76-79 with lib/utils/image.py:196-234: v / 255, brightness / contrast / saturation in the
+// item's order, lighting, (x - mean) / std -- float32, every operation rounded once.  The contrast step blends with the
+// mean grey value of the WHOLE crop, so the work is two launches: crop_sum_kernel leaves the crop's bytes (planar:
+// crop_u8[item][c][pixel]) and the three channel sums of every item, color_aug_kernel reads both.
+// The sums are INTEGERS (every pixel of the crop is a byte): one 64-bit integer atomic add per channel and workgroup.
+// Integer addition gives the same bits in any order, so the result does not depend on the order the workgroups arrive
+// in -- this is why an atomic is allowed here while every floating-point reduction of the library has a fixed order.
+constexpr int kAug = 16;           // 4-byte words per aug row: int32 {on, order[3]}, float32 {a[3], om[3], d[3]}, 3 unused
+
+__global__ void __launch_bounds__(kThreads) zero_sums_kernel(unsigned long long *__restrict__ sums, int n) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i < n) sums[i] = 0ull;
+}
+
+__global__ void __launch_bounds__(kThreads)
+crop_sum_kernel(const unsigned char *__restrict__ arena, const double *__restrict__ items,
+                unsigned char *__restrict__ crop_u8, unsigned long long *__restrict__ sums, int out_h, int out_w) {
+  __shared__ unsigned s_part[kThreads / 64][3];
+  const int item = blockIdx.y;
+  const int hw = out_h * out_w;
+  const int pix = blockIdx.x * kThreads + threadIdx.x;
+  int v[3] = {0, 0, 0};                       // a lane past the plane adds 0
+  if (pix < hw) {
+    const int y = pix / out_w, x = pix - y * out_w;
+    crop_pixel(arena, items + (size_t)item * kItem, x, y, v);
+    unsigned char *o = crop_u8 + (size_t)item * 3 * hw + pix;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[(size_t)c * hw] = (unsigned char)v[c];
+  }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] += __shfl_xor(v[c], m, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s_part[threadIdx.x >> 6][c] = (unsigned)v[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned t = 0;                           // <= 256 * 255
+#pragma unroll
+    for (int wv = 0; wv < kThreads / 64; ++wv) t += s_part[wv][threadIdx.x];
+    atomicAdd(sums + (size_t)item * 3 + threadIdx.x, (unsigned long long)t);
+  }
+}
+
+__global__ void __launch_bounds__(kThreads)
+color_aug_kernel(const unsigned char *__restrict__ crop_u8, const unsigned long long *__restrict__ sums,
+                 const float *__restrict__ aug, const float *__restrict__ mean_std, float *__restrict__ out, int out_h,
+                 int out_w) {
+#pragma clang fp contract(off)
+  __shared__ float s_gs_mean;
+  const int item = blockIdx.y;
+  const int hw = out_h * out_w;
+  const float *__restrict__ row = aug + (size_t)item * kAug;      // uniform over the workgroup: scalar loads
+  const int *__restrict__ rowi = reinterpret_cast<const int *>(row);
+  const bool on = rowi[0] != 0;
+  if (on && threadIdx.x == 0) {
+    // float64, float64 literals, every operation rounded on its own; the sums are exact in a double (< 2^39)
+    const double s0 = (double)sums[(size_t)item * 3], s1 = (double)sums[(size_t)item * 3 + 1],
+                 s2 = (double)sums[(size_t)item * 3 + 2];
+    const double p0 = 0.114 * s0, p1 = 0.587 * s1, p2 = 0.299 * s2;
+    const double num = (p0 + p1) + p2;
+    const double den = 255.0 * (double)hw;
+    s_gs_mean = (float)(num / den);
+  }
+  __syncthreads();
+  const int pix = blockIdx.x * kThreads + threadIdx.x;
+  if (pix >= hw) return;
+  const unsigned char *p = crop_u8 + (size_t)item * 3 * hw + pix;
+  float x[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) x[c] = (float)p[(size_t)c * hw] / 255.0f;
+  if (on) {
+    const float gs_mean = s_gs_mean;
+    const float g0 = x[0] * 0.114f, g1 = x[1] * 0.587f, g2 = x[2] * 0.299f;
+    const float gs = (g0 + g1) + g2;          // of the un-augmented pixel, once (image.py:230)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int f = rowi[1 + k] & 3;      // (the host admits 0, 1, 2 only; the mask keeps any word inside the row)
+      const float a = row[4 + f], om = row[7 + f];
+      if (f == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[c] = x[c] * a;
+      } else {
+        const float q = (f == 1 ? gs_mean : gs) * om;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float t = x[c] * a;
+          x[c] = t + q;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = x[c] + row[10 + c];
+  }
+  float *o = out + (size_t)item * 3 * hw + pix;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float t = x[c] - mean_std[c];
+    o[(size_t)c * hw] = t / mean_std[3 + c];
   }
 }
 
@@ -148,4 +262,27 @@ extern "C" int cdn_ctdet_pre_process(const unsigned char *src_arena, const doubl
   pre_process_kernel<<<grid, kThreads, 0, cdn::as_stream(stream)>>>(src_arena, items, lut, out, (int)out_h, (int)out_w,
                                                                     (int)P, mirror ? 1 : 0);
   return cdn::check_launch("ctdet pre_process");
+}
+
+extern "C" int cdn_ctdet_pre_process_aug(const unsigned char *src_arena, const double *items, int64_t P, const float *aug,
+                                         const float *mean_std, unsigned char *crop_u8, unsigned long long *sums,
+                                         float *out, int64_t out_h, int64_t out_w, void *stream) {
+  CDN_REQUIRE(src_arena && items && aug && mean_std && crop_u8 && sums && out, CDN_ERR_ARG, "null pointer");
+  CDN_REQUIRE(P > 0 && out_h > 0 && out_w > 0, CDN_ERR_ARG, "non-positive size");
+  CDN_REQUIRE(P <= 65535, CDN_ERR_UNSUPPORTED, "more than 65535 items in one call");
+  CDN_REQUIRE(out_h <= (1 << 20) && out_w <= (1 << 20) && out_h * out_w < (int64_t(1) << 31) - kThreads,
+              CDN_ERR_UNSUPPORTED, "output plane %lld x %lld too large", (long long)out_h, (long long)out_w);
+  hipStream_t st = cdn::as_stream(stream);
+  // the sums start from zero in every call: a launch of our own in front of the kernel that adds, hence a node of a
+  // captured graph.  NOT hipMemsetAsync: the runtime's memset node filled the sums with a stale 16-byte pattern on the
+  // second replay of a captured run
+  zero_sums_kernel<<<(unsigned)cdn::ceil_div(P * 3, kThreads), kThreads, 0, st>>>(sums, (int)(P * 3));
+  const int rz = cdn::check_launch("ctdet zero_sums");
+  if (rz != CDN_OK) return rz;
+  const dim3 grid((unsigned)cdn::ceil_div(out_h * out_w, kThreads), (unsigned)P);
+  crop_sum_kernel<<<grid, kThreads, 0, st>>>(src_arena, items, crop_u8, sums, (int)out_h, (int)out_w);
+  const int rc = cdn::check_launch("ctdet crop_sum");
+  if (rc != CDN_OK) return rc;
+  color_aug_kernel<<<grid, kThreads, 0, st>>>(crop_u8, sums, aug, mean_std, out, (int)out_h, (int)out_w);
+  return cdn::check_launch("ctdet color_aug");
 }

@@ -969,6 +969,32 @@ int cdn_ctdet_pre_process(const unsigned char *src_arena, const double *items, i
                           int64_t out_h, int64_t out_w, int mirror, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The default training sample's input: the crop above followed by color_aug (lib/datasets/sample/ctdet.py:76-79 with
+ * lib/utils/image.py:196-234): v / 255, brightness / contrast / saturation in a shuffled order, lighting,
+ * (x - mean) / std.  The arithmetic is DESIGN.md section 7.4c (tests/color_aug_ref.py restates it; the kernels equal it
+ * bit for bit): float32, every operation rounded once, no contraction; the contrast step's whole-crop grey mean comes
+ * from EXACT integer channel sums, gs_mean = float32(((0.114 S0 + 0.587 S1) + 0.299 S2) / (255.0 N)) in double.
+ *
+ * cdn_ctdet_pre_process_aug: three launches on `stream` -- zero_sums_kernel clears `sums`, then crop_sum_kernel and
+ * color_aug_kernel; capturable (the clearing is a kernel node of the graph: the runtime's memset node is avoided,
+ * DESIGN.md section 7.4c); the launch geometry depends on P, out_h and out_w only.
+ *   src_arena, items   as cdn_ctdet_pre_process
+ *   aug        DEVICE [P][16] 4-byte words per item: int32 on, int32 order[3] (a permutation of 0 brightness, 1 contrast,
+ *              2 saturation), float32 a[3] = float32(alpha_k), float32 om[3] = float32(1 - alpha_k), float32 d[3] (the
+ *              lighting term per channel position), 3 unused.  on == 0 (validation split, --no_color_aug): the item is
+ *              ((float32(v) / 255f) - mean) / std, the float32 chain of the reference's sample.  The host checks the rows.
+ *   mean_std   DEVICE float32 [6]: mean[3], std[3], by channel position
+ *   crop_u8    DEVICE scratch, P * 3 * out_h * out_w bytes: the crops as planes, crop_u8[item][c][y][x]
+ *   sums       DEVICE uint64 [P][3]: on return (in stream order) S_c = the sum of channel c over all out_h * out_w
+ *              pixels of the item's crop, border included.  Integer atomic adds: any order gives the same bits.
+ *   out        float32 [P][3][out_h][out_w]
+ * P <= 65535, out_h * out_w < 2^31 (CDN_ERR_UNSUPPORTED beyond); null pointers: CDN_ERR_ARG, before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_ctdet_pre_process_aug(const unsigned char *src_arena, const double *items, int64_t P, const float *aug,
+                              const float *mean_std, unsigned char *crop_u8, unsigned long long *sums, float *out,
+                              int64_t out_h, int64_t out_w, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The ctdet training criterion (main.py / quant_main.py: ModelWithLoss -> CtdetLoss, lib/trains/ctdet.py:17-74) and
  * the target maps it is fed (lib/datasets/sample/ctdet.py:87-122).  codenet_loss.hip; Python: codenet_amd/losses.py.
  *

@@ -62,7 +62,9 @@ BUDGET_LOSS = {"ctdet_loss_fwd_kernel": 64, "ctdet_loss_bwd_kernel": 64, "ctdet_
                "ctdet_targets_kernel": 128}
 # codenet_preproc.hip: one thread per output pixel, bound by its stores -- eight waves per SIMD (64 VGPRs; 52 when it was
 # written, with the double geometry and the recomputed resize taps), no scratch
-BUDGET_PREPROC = {"pre_process_kernel": 64}
+# (the crop is a __device__ function shared with crop_sum_kernel: 52 / 51 VGPRs); color_aug_kernel is bound by its 12 bytes
+# of stores per pixel: 18 VGPRs when it was written
+BUDGET_PREPROC = {"pre_process_kernel": 64, "crop_sum_kernel": 64, "color_aug_kernel": 64}
 
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
