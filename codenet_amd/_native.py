@@ -161,6 +161,12 @@ _SIGNATURES = {
     "cdn_ctdet_loss_forward": (_i, [_vp] * 8 + [_i64] * 5 + [_i] * 3 + [_f] * 3 + [_vp] * 3 + [ctypes.c_size_t, _vp]),
     "cdn_ctdet_loss_backward": (_i, [_vp] * 8 + [_i64] * 5 + [_i] * 2 + [_f] * 3 + [_vp] * 6),
     "cdn_ctdet_targets": (_i, [_vp] * 3 + [_i64] * 5 + [_vp] * 6),
+    "cdn_codenet_head_act_update": (_i, [_vp] * 4 + [_i64, _i, _d, _i, _i, _vp, _vp]),
+    "cdn_codenet_head_dw_forward": (_i, [_vp] * 5 + [_i64] * 4 + [_vp] * 4 + [_i, _d, _i, _vp, _vp]),
+    "cdn_codenet_head_tail_train_forward": (_i, [_vp] * 5 + [_i64] * 4 + [_vp]),
+    "cdn_codenet_head_dw_backward_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
+    "cdn_codenet_head_dw_backward": (_i, [_vp, _vp, _i64] + [_vp] * 5 + [_i64, _vp, _vp] + [_i64] * 4
+                                     + [_vp, ctypes.c_size_t, _vp]),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

@@ -230,7 +230,9 @@ class PoseShuffleNetV2(nn.Module):
         else:
             from .functions.codenet_stage import forward_stage_blocks
             x = forward_stage_blocks(self.deconv_layers, x)      # == self.deconv_layers(x); fused blocks in the QAT step
-        return [{head: getattr(self, head)(x) for head in self.heads}]
+        from .functions.codenet_heads import forward_heads
+        # == {head: getattr(self, head)(x)}; the quantised heads of a QAT step as one native autograd function
+        return [forward_heads({head: getattr(self, head) for head in self.heads}, x)]
 
 
 def fill_state_dict_(model, seed=317):

@@ -1,4 +1,4 @@
-"""GraphedTrainStep: the QAT step of the deform-stage stack as one HIP graph.
+"""GraphedTrainStep: the QAT step of the deform-stage stack -- or of the detection tail, stages + heads -- as one HIP graph.
 
 Part of codenet_amd.pipeline (split by concern in round 6; `from codenet_amd import pipeline` exposes every name as
 before)."""
@@ -7,6 +7,42 @@ import os
 import torch
 import torch.nn as nn
 
+
+class DetectionTail(nn.Module):
+    """Everything of the CoDeNet behind the backbone as one module: the deform stages and the detection heads of `model`
+    (a harness.PoseShuffleNetV2; the modules are SHARED, not copied).  forward(feat) -> [{head: tensor}] from a layer-4
+    feature map, as the model's own forward returns it.  After quantisation every kernel of its training step is this
+    library's (functions/codenet_stage.forward_stage_blocks, functions/codenet_heads.forward_heads)."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.heads = dict(model.heads)
+        self.deconv_layers = model.deconv_layers
+        for h in self.heads:
+            setattr(self, h, getattr(model, h))
+
+    def head_modules(self):
+        return {h: getattr(self, h) for h in self.heads}
+
+    def forward(self, feat):
+        from ..functions.codenet_heads import forward_heads
+        from ..functions.codenet_stage import forward_stage_blocks
+        return [forward_heads(self.head_modules(), forward_stage_blocks(self.deconv_layers, feat))]
+
+
+def _stage_blocks_ok(seq):
+    """A Sequential of [quantised deform stage, Sequential(ReLU, QuantAct), Upsample] blocks."""
+    from ..portable_quantizer.quant_modules import QuantAct, QuantDeformConvWithOffsetScaleBoundPositive
+    if not isinstance(seq, nn.Sequential) or len(seq) == 0 or len(seq) % 3:
+        return False
+    mods = list(seq)
+    for i in range(0, len(mods), 3):
+        q, post, up = mods[i:i + 3]
+        if not (isinstance(q, QuantDeformConvWithOffsetScaleBoundPositive) and isinstance(post, nn.Sequential)
+                and len(post) == 2 and isinstance(post[0], nn.ReLU) and isinstance(post[1], QuantAct)
+                and isinstance(up, nn.Upsample)):
+            return False
+    return True
 
 
 class GraphedTrainStep:
@@ -27,13 +63,16 @@ class GraphedTrainStep:
     exactly as in the eager loop.  `warmup` eager steps run first on a side stream (they DO train: allocator and lazily
     derived tensors settle before capture); the capture records on that same stream.
 
-    SCOPE (round 6).  Validated -- and accepted without `unvalidated=True` -- is the stack of deform stages
-    (``pipeline.build_hot_path`` / a quantised ``deconv_layers``): every kernel of that step is this library's, every sum
-    has one order, and tests/test_train_step.py::test_graphed_train_step_* show replays bit-identical to the eager step and
+    SCOPE.  Validated -- and accepted without `unvalidated=True` -- are (1) the stack of deform stages
+    (``pipeline.build_hot_path`` / a quantised ``deconv_layers``, `is_stage_stack`) and (2) the detection tail,
+    ``pipeline.DetectionTail(model)`` of a quantised model whose heads run on functions/codenet_heads.py
+    (`is_native_tail`): every kernel of those steps is this library's, every sum has one order.
+    tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
     bit-identical from a restored state whatever else the process does in between (a second model built before the capture
-    taking its first eager steps, another framework model training, the allocator's free memory filled with NaN).
-    A network that also runs PyTorch-ROCm operators under autograd (the whole CoDeNet: backbone and heads) needs
-    `unvalidated=True`; what was measured for it (tools/experiments/gts_probe*.py):
+    taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
+    tests/test_gpu_heads_train.py shows replays of (2) with the native criterion bit-identical to the eager steps.
+    A network that also runs PyTorch-ROCm operators under autograd (the whole CoDeNet with its backbone, fp32 or
+    percentile heads, NATIVE_HEADS off) needs `unvalidated=True`; what was measured for it (tools/experiments/gts_probe*.py):
       * parameters and gradients of a replay agree with any other replay FROM THE SAME STATE to ~1e-6 of their magnitude --
         with or without other work in between.  That residue is the framework's own backward (atomics), present in two
         eager runs too; after a quantiser amplifies it the loss trajectories of two runs part ways in the fifth digit by
@@ -47,9 +86,10 @@ class GraphedTrainStep:
         (``codenet_amd.losses.CtdetLoss``: its sums are fixed-order slabs of this library's own kernels)."""
 
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
-        if not unvalidated and not self.is_stage_stack(net):
+        if not unvalidated and not self.is_stage_stack(net) and not self.is_native_tail(net):
             raise NotImplementedError(
-                "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages only; `net` "
+                "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages and for a "
+                "pipeline.DetectionTail whose heads run natively only; `net` "
                 "holds other modules, whose PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass "
                 "unvalidated=True to capture it anyway (see the class docstring for what was measured).")
         self.static = [t.detach().clone() for t in example_inputs]
@@ -76,20 +116,22 @@ class GraphedTrainStep:
     def is_stage_stack(net):
         """True for a (container of one) Sequential of [quantised deform stage, Sequential(ReLU, QuantAct), Upsample]
         blocks -- what functions/codenet_stage.forward_stage_blocks runs natively and the bit-level tests cover."""
-        from ..portable_quantizer.quant_modules import QuantAct, QuantDeformConvWithOffsetScaleBoundPositive
         seq = getattr(net, "deconv_layers", net)
         if not isinstance(seq, nn.Sequential) or len(seq) == 0 or len(seq) % 3:
             return False
         if seq is not net and [m for m in net.children()] != [seq]:
             return False
-        mods = list(seq)
-        for i in range(0, len(mods), 3):
-            q, post, up = mods[i:i + 3]
-            if not (isinstance(q, QuantDeformConvWithOffsetScaleBoundPositive) and isinstance(post, nn.Sequential)
-                    and len(post) == 2 and isinstance(post[0], nn.ReLU) and isinstance(post[1], QuantAct)
-                    and isinstance(up, nn.Upsample)):
-                return False
-        return True
+        return _stage_blocks_ok(seq)
+
+    @staticmethod
+    def is_native_tail(net):
+        """True for a pipeline.DetectionTail whose stages are the blocks `is_stage_stack` accepts and whose heads
+        functions/codenet_heads.forward_heads runs natively (native_reason(heads, None) is None: quantised heads with
+        the default QuantAct settings, no hooks, NATIVE_HEADS on) -- stages, heads and, with losses.CtdetLoss, the
+        criterion are then one chain of this library's kernels."""
+        from ..functions.codenet_heads import native_reason
+        return (isinstance(net, DetectionTail) and _stage_blocks_ok(net.deconv_layers)
+                and native_reason(net.head_modules(), None) is None)
 
     def set_lr(self, value, group=None):
         """Write a new learning rate where the captured step reads it: the param group's lr must be a device TENSOR

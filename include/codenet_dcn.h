@@ -1054,6 +1054,47 @@ int cdn_ctdet_targets(const float *boxes, const int32_t *classes, const int32_t 
                       void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The quantised detection heads in the QAT step (QuantDepthwiseNode, quant_modules.py:1013-1071), per head:
+ *   y1 = conv1x1(x, W1q) + b1,  a1 = fq1(relu(y1)),  r2 = relu(dw3x3(a1, W2q, zero padding) + b2),  y3 = conv1x1(fq3(r2), W3q) + b3
+ * NCHW fp32.  The dense 1x1 convolutions and their gradients are cdn_codenet_pointwise_forward[_range] /
+ * cdn_codenet_pointwise_wgrad[_q]; these are the pieces in between.  Every call takes a stream, allocates nothing, launches
+ * no memset node and is capturable; every floating-point sum has one order (no float atomics).
+ *
+ * cdn_codenet_head_act_update: the QuantAct update (range tracking when running != 0, then scale / zero point) from the
+ *   {min, max} pairs a producer left (`partials`, float2 [n_partials]; ignored with running == 0); relu != 0: the extremes
+ *   are those of max(x, 0).  state_copy (8 words, may be NULL) receives the snapshot a backward pass reads.  One launch.
+ * cdn_codenet_head_dw_forward: r2 [N][C][H][W] from y1, with a1 formed while loading (a1_state: the 8-word state or
+ *   snapshot of the QuantAct behind y1); taps outside the plane are 0.0f.  r2 is stored BEFORE quantisation.  running != 0:
+ *   the launch's last workgroup updates the QuantAct behind r2 (x_min, x_max, state, counters =
+ *   cdn_quantact_arrive_words() zero words, left zero) from the extremes of r2 and writes state_copy (may be NULL);
+ *   running == 0: the QuantAct arguments are not read.
+ * cdn_codenet_head_tail_train_forward: y3 [N][Co][HW] = W3q [Co][C] . fq(r2) + b3 (may be NULL) for 1 <= Co <= 4
+ *   (CDN_ERR_UNSUPPORTED beyond), a2_state: the state of the QuantAct behind r2.
+ * cdn_codenet_head_dw_backward:
+ *   Co == 0: g = grad_a2 [N][C][H][W];   1 <= Co <= 4: g = grad_y3 [N][Co][H][W] and w3 = W3q [Co][C] -- the kernel
+ *            forms grad_a2[c] = sum_o W3q[o][c] grad_y3[o] itself (o ascending) and never stores it
+ *   grad_y2 = grad_a2 where r2 > 0;  grad_y1 = (sum_t W2q[c][t] grad_y2[q - t]) where y1 > 0 -- a gather;
+ *   grad_y1 is written at grad_y1 + n * grad_y1_image_pitch + c * H * W (elements): a channel slice of a wider buffer
+ *   grad_w2 [C][9], grad_b2 [C] (either may be NULL): OVERWRITTEN; per-workgroup partials in `workspace`
+ *   (cdn_codenet_head_dw_backward_workspace_bytes, 16-byte aligned, every word written before it is read) summed in index
+ *   order by a second launch.
+ * 16-byte loads where W % 4 == 0 and the pointers (and the pitch) are 16-byte aligned, scalar loads otherwise.
+ * N * C * H * W < 2^31 (CDN_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_codenet_head_act_update(float *x_min, float *x_max, void *state, const float *partials, int64_t n_partials,
+                                int bits, double momentum, int running, int relu, void *state_copy, void *stream);
+int cdn_codenet_head_dw_forward(const float *y1, const void *a1_state, const float *w2, const float *b2, float *r2,
+                                int64_t N, int64_t C, int64_t H, int64_t W, float *x_min, float *x_max, void *state,
+                                void *counters, int bits, double momentum, int running, void *state_copy, void *stream);
+int cdn_codenet_head_tail_train_forward(const float *r2, const void *a2_state, const float *w3, const float *b3, float *y3,
+                                        int64_t N, int64_t C, int64_t Co, int64_t HW, void *stream);
+size_t cdn_codenet_head_dw_backward_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W);
+int cdn_codenet_head_dw_backward(const float *g, const float *w3, int64_t Co, const float *r2, const float *y1,
+                                 const void *a1_state, const float *w2, float *grad_y1, int64_t grad_y1_image_pitch,
+                                 float *grad_w2, float *grad_b2, int64_t N, int64_t C, int64_t H, int64_t W,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

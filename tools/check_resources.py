@@ -65,6 +65,12 @@ BUDGET_LOSS = {"ctdet_loss_fwd_kernel": 64, "ctdet_loss_bwd_kernel": 64, "ctdet_
 # (the crop is a __device__ function shared with crop_sum_kernel: 52 / 51 VGPRs); color_aug_kernel is bound by its 12 bytes
 # of stores per pixel: 18 VGPRs when it was written
 BUDGET_PREPROC = {"pre_process_kernel": 64, "crop_sum_kernel": 64, "color_aug_kernel": 64}
+# codenet_heads_train.hip (built without the SLP vectoriser, as codenet_train.hip): bandwidth-bound register-window
+# kernels that hide latency with occupancy -- the depthwise forward and the small tail at eight waves per SIMD (64 VGPRs;
+# 46-50 / 37-54 when written), the depthwise backward with its two 3 x 6 windows and ten sums at four (128; 73-104), no
+# scratch
+BUDGET_HEADS_TRAIN = {"head_dw_fwd_kernel": 64, "head_tail_fwd_kernel": 64, "head_dw_bwd_kernelILi": 128,
+                      "head_dw_bwd_reduce_kernel": 64}
 
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
@@ -100,7 +106,8 @@ def check():
     res.update(res_l)
     for src, extra, budget in (("codenet_stage.hip", ("-fno-slp-vectorize",), BUDGET_STAGE), ("dcn_generic.hip", (), BUDGET_GENERIC),
                                ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE),
-                               ("codenet_loss.hip", (), BUDGET_LOSS), ("codenet_preproc.hip", (), BUDGET_PREPROC)):
+                               ("codenet_loss.hip", (), BUDGET_LOSS), ("codenet_preproc.hip", (), BUDGET_PREPROC),
+                               ("codenet_heads_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_TRAIN)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -127,7 +134,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))
