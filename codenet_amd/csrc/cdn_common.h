@@ -234,6 +234,36 @@ __device__ __forceinline__ float fake_quant_r(float x, float scale, float zp, fl
   const float q0 = __fmul_rn(n, r);
   return fmaf(fmaf(-q0, scale, n), r, q0);
 }
+// ---- int8 activation codes in HBM (frozen-range schedule, codenet_frozen.hip) -------------------------
+// A frozen QuantAct (running_stat = False, quant_modules.py:203-219 skipped) has a fixed (scale, zp), so its
+// output can cross HBM as ONE byte per element: the code q = round(scale*x - zp) itself (quant_utils.py:33-41,
+// 60-75), which lies in [-128,127] for every x inside the frozen range; the value every consumer sees is
+// (q + zp) / scale, exactly what the fp32 schedule materialises (the level L = q + zp is NOT byte sized: it runs
+// from round(scale*x_min) to round(scale*x_min) + 255).  The reference does not clamp q (quant_utils.py:193-200);
+// a byte must: a code outside
+// [-128,127] is saturated AND reported through a device flag -- the caller then recomputes that batch on the
+// fp32 schedule.  Rounding: the 1.5*2^23 trick, as in pwi8_kernel::ucode (round-half-even of the reference's
+// two-rounding expression); values too large for the trick land far outside int8 and are flagged as well.
+struct Code8 {
+  float qs, qz;
+};
+using BadMask = int;     // per-lane: non-zero when some code of this lane saturated
+__device__ __forceinline__ Code8 make_code8(const unsigned *state, BadMask &bad) {
+  Code8 c;
+  c.qs = reinterpret_cast<const float *>(state)[2];
+  c.qz = reinterpret_cast<const float *>(state)[3];
+  if (!(fabsf(c.qz) < 4.0e6f)) bad = 1;          // degenerate range (zp must stay an exactly representable integer)
+  return c;
+}
+__device__ __forceinline__ int act_code8(float v, const Code8 &c, BadMask &bad) {
+#pragma clang fp contract(off)
+  const float y_p = c.qs * v;      // (plain operators under fp contract(off): two roundings, see quant_code)
+  const float y = (y_p - c.qz) + 12582912.0f;
+  const int a = (int)__float_as_uint(y) - 0x4B400000;      // rint(scale*v - zp)
+  const int s = min(max(a, -128), 127);
+  bad |= a ^ s;          // (non-zero iff the clamp changed the code: one xor + one or, no compare)
+  return s;
+}
 // ---- QuantAct range tracking + parameters, one thread (quant_modules.py:211-219,
 // quant_utils.py:60-75); shared by the stand-alone update kernel and the in-kernel
 // "last workgroup" update of the fused schedule.  have_stats: bmin/bmax are this batch's extremes.
@@ -243,6 +273,8 @@ struct QUpdate {
   unsigned *counters;    // fused schedule only: kArriveWords zero-initialised arrival counters
   float m_minus_1, one_minus_m;
   int bits, running;
+  // this launch measures its output's range: the producer ends with block_minmax_finish
+  __host__ __device__ bool tracks() const { return counters != nullptr; }
 };
 // Arrival counters: 64 group counters + 1 top counter, one per 64-byte line (a single contended
 // word sustains only ~88 atomics/us; 2048 workgroups on one word cost ~25 us).
@@ -322,10 +354,9 @@ __device__ __forceinline__ void lds_barrier() {
 // arrivals (a single contended word sustains only ~88 atomics/us).  Lines start at zero and the last
 // arriver zeroes them again.  Cross-workgroup visibility: agent-scope atomics on both sides (sc1,
 // bypassing the non-coherent L1s).  Every thread of the workgroup must call this; `red` is
-// >= 2*nwaves + 2 floats of free LDS.  (`partials` is unused by this protocol.)
-__device__ __forceinline__ void block_minmax_finish(float mn, float mx, float2 *partials, int bid,
-                                                    int nblocks, const QUpdate &u, float *red) {
-  (void)partials;
+// >= 2*nwaves + 2 floats of free LDS.  A kernel runs it iff u.tracks() (the launch was given arrival counters).
+__device__ __forceinline__ void block_minmax_finish(float mn, float mx, int bid, int nblocks, const QUpdate &u,
+                                                    float *red) {
   // (keys: see "NaN-propagating range reductions" above; mn / mx may be the poisoned pair of nan_lo / nan_hi)
   unsigned klo = key_lo(mn), khi = key_hi(mx);
   wave_key_max(klo, khi);
@@ -419,8 +450,11 @@ __device__ __forceinline__ void block_minmax_store(float mn, float mx, float2 *o
 #endif
 
 namespace cdn {
-// per-kernel capacity of the {min,max} partial arrays; grids are clamped / checked against it
-constexpr int kMaxPartials = 16384;
+// most workgroups a launch of the fused / layer / frozen schedules may have: grids are clamped / checked against it
+constexpr int kMaxGrid = 16384;
+// bytes of one RESERVED region of the ABI-1 workspaces (where per-workgroup {min,max} partial arrays used to live:
+// nothing reads or writes them; the sizes and offsets stay until the ABI version moves)
+constexpr size_t kReservedRegionBytes = 16384 * 8;
 // codenet_fused.hip, shared with the frozen-range schedule (codenet_frozen.hip)
 int stage_channel_chunk(int Hl, int Wl);
 int thin_channel_chunk(int cch, int64_t C, int64_t N);
@@ -444,14 +478,11 @@ int launch_frozen_dw(const void *x, int x_kind, const unsigned *xq, const float 
                      const float *wd, signed char *d8, unsigned *dstate, unsigned *oflow, int N, int C, int H, int W,
                      int up, hipStream_t st, ScaleFromSums si = ScaleFromSums{nullptr, nullptr, nullptr, 0.f, 0.f},
                      int gmode = 0);
-// Workspace of the stand-alone layer entry points: partials first, arrival counters in the LAST bytes
-// (zeroed once by the caller); size = cdn_codenet_aux_workspace_bytes().
-struct AuxWs {
-  float2 *partials;
-  unsigned *arrive;
-};
+// Workspace of the stand-alone layer entry points: one reserved region, then the arrival counters in the LAST bytes
+// (zeroed once by the caller); size = cdn_codenet_aux_workspace_bytes().  Returns the counters, nullptr when the
+// workspace is missing or too small.
 size_t aux_workspace_bytes();
-bool aux_workspace(void *workspace, size_t bytes, AuxWs *w);
+unsigned *aux_workspace(void *workspace, size_t bytes);
 }  // namespace cdn
 
 #define CDN_REQUIRE(cond, code, ...) \

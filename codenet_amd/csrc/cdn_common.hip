@@ -121,15 +121,12 @@ extern "C" const char *cdn_last_error(void) { return cdn::err_buf(); }
 namespace cdn {
 size_t aux_workspace_bytes() {
   auto r = [](size_t b) { return (b + 255) / 256 * 256; };
-  return r((size_t)kMaxPartials * 8) + r((size_t)kArriveWords * 4);
+  return r(kReservedRegionBytes) + r((size_t)kArriveWords * 4);
 }
-bool aux_workspace(void *workspace, size_t bytes, AuxWs *w) {
+unsigned *aux_workspace(void *workspace, size_t bytes) {
   if (!workspace || bytes < aux_workspace_bytes() || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0)
-    return false;
-  char *p = static_cast<char *>(workspace);
+    return nullptr;
   const size_t cnt = ((size_t)kArriveWords * 4 + 255) / 256 * 256;
-  w->partials = reinterpret_cast<float2 *>(p);
-  w->arrive = reinterpret_cast<unsigned *>(p + bytes / 256 * 256 - cnt);
-  return true;
+  return reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + bytes / 256 * 256 - cnt);
 }
 }  // namespace cdn

@@ -24,26 +24,10 @@ namespace {
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 using i32x16 = __attribute__((ext_vector_type(16))) int;
 
-struct Code8 {   // (same as codenet_fused.hip: the byte is the code q = round(scale*x - zp) itself)
-  float qs, qz;
-};
-using BadMask = int;
-__device__ __forceinline__ Code8 make_code8(const unsigned *state, BadMask &bad) {
-  Code8 c;
-  c.qs = reinterpret_cast<const float *>(state)[2];
-  c.qz = reinterpret_cast<const float *>(state)[3];
-  if (!(fabsf(c.qz) < 4.0e6f)) bad = 1;
-  return c;
-}
-__device__ __forceinline__ int act_code8(float v, const Code8 &c, BadMask &bad) {
-#pragma clang fp contract(off)
-  const float y_p = c.qs * v;      // (plain operators under fp contract(off): two roundings, cdn_common.h)
-  const float y = (y_p - c.qz) + 12582912.0f;
-  const int a = (int)__float_as_uint(y) - 0x4B400000;      // rint(scale*v - zp)
-  const int s = min(max(a, -128), 127);
-  bad |= a ^ s;
-  return s;
-}
+using cdn::BadMask;      // (byte codes: cdn_common.h)
+using cdn::Code8;
+using cdn::act_code8;
+using cdn::make_code8;
 
 // ------------------------------------------------------------------------------------------------------
 // frozen_params_kernel: (scale, zero-point) of up to 64 frozen QuantActs from their x_min / x_max buffers
@@ -652,21 +636,6 @@ maxq8_kernel(const signed char *__restrict__ a8, signed char *__restrict__ out8,
 }  // namespace
 
 static int frozen_params_impl(int n, float *const *x_min, float *const *x_max, void *const *state, int bits,
-                              void *zero, size_t zero_bytes, void *stream);
-
-extern "C" int cdn_quantact_frozen_params(int n, float *const *x_min, float *const *x_max, void *const *state,
-                                          int bits, void *stream) {
-  return frozen_params_impl(n, x_min, x_max, state, bits, nullptr, 0, stream);
-}
-
-extern "C" int cdn_quantact_frozen_params_clear(int n, float *const *x_min, float *const *x_max, void *const *state,
-                                                int bits, void *clear, size_t clear_bytes, void *stream) {
-  CDN_REQUIRE(clear_bytes == 0 || (clear && (reinterpret_cast<uintptr_t>(clear) & 15) == 0 && (clear_bytes & 15) == 0),
-              CDN_ERR_ARG, "the buffer to clear must be 16-byte aligned and a multiple of 16 bytes");
-  return frozen_params_impl(n, x_min, x_max, state, bits, clear, clear_bytes, stream);
-}
-
-static int frozen_params_impl(int n, float *const *x_min, float *const *x_max, void *const *state, int bits,
                               void *zero, size_t zero_bytes, void *stream) {
   CDN_REQUIRE(n >= 0 && n <= kMaxFrozen, CDN_ERR_ARG, "at most %d QuantActs per call", kMaxFrozen);
   CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
@@ -687,6 +656,18 @@ static int frozen_params_impl(int n, float *const *x_min, float *const *x_max, v
   const int zblocks = (int)std::min<long>(cdn::ceil_div(f.zero_n16, 256 * 4), 256);
   frozen_params_kernel<<<1 + zblocks, 256, 0, cdn::as_stream(stream)>>>(f);
   return cdn::check_launch("frozen QuantAct parameters");
+}
+
+extern "C" int cdn_quantact_frozen_params(int n, float *const *x_min, float *const *x_max, void *const *state,
+                                          int bits, void *stream) {
+  return frozen_params_impl(n, x_min, x_max, state, bits, nullptr, 0, stream);
+}
+
+extern "C" int cdn_quantact_frozen_params_clear(int n, float *const *x_min, float *const *x_max, void *const *state,
+                                                int bits, void *clear, size_t clear_bytes, void *stream) {
+  CDN_REQUIRE(clear_bytes == 0 || (clear && (reinterpret_cast<uintptr_t>(clear) & 15) == 0 && (clear_bytes & 15) == 0),
+              CDN_ERR_ARG, "the buffer to clear must be 16-byte aligned and a multiple of 16 bytes");
+  return frozen_params_impl(n, x_min, x_max, state, bits, clear, clear_bytes, stream);
 }
 
 extern "C" size_t cdn_codenet_stage_frozen_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int x_up) {

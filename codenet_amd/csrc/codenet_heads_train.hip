@@ -146,7 +146,7 @@ head_dw_fwd_kernel(const float *__restrict__ y1, const unsigned *__restrict__ a1
     }
   }
   if (qu.counters) {
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), nullptr, (int)blockIdx.x, (int)gridDim.x, qu,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), (int)blockIdx.x, (int)gridDim.x, qu,
                              red);
     cdn::last_block_state_copy(qu, state_copy, red);
   }

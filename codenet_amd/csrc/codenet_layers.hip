@@ -15,7 +15,7 @@
 namespace {
 
 using cdn::fake_quant;
-using cdn::kMaxPartials;
+using cdn::kMaxGrid;
 using i32x4 = __attribute__((ext_vector_type(4))) int;
 using i32x16 = __attribute__((ext_vector_type(16))) int;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
@@ -41,7 +41,7 @@ template <bool XQ, int UP, int STRIDE, int CCH>
 __global__ void __launch_bounds__(256)
 dw3_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, const float *__restrict__ w,
            const float *__restrict__ bias, const float *__restrict__ ep_scale,
-           const float *__restrict__ ep_shift, float *__restrict__ out, float2 *mm, cdn::QUpdate qu,
+           const float *__restrict__ ep_shift, float *__restrict__ out, cdn::QUpdate qu,
            int C, int ld_in, int ld_out, int Hs, int Ws, int relu, int nbands,
            const unsigned char *__restrict__ agen) {
   extern __shared__ float4 band4[];         // [rows][Ws + 2][CCH / 4 quads]
@@ -175,9 +175,9 @@ dw3_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, const f
           }
       }
   }
-  if (mm) {
+  if (qu.tracks()) {
     __syncthreads();
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), mm, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
                              reinterpret_cast<float *>(band4));
   }
 }
@@ -197,7 +197,7 @@ template <bool XQ, int STRIDE, int CCH, int MAXL>
 __global__ void __launch_bounds__(256)
 dws_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, const unsigned char *__restrict__ agen,
            const float *__restrict__ w, const float *__restrict__ bias, const float *__restrict__ ep_scale,
-           const float *__restrict__ ep_shift, float *__restrict__ out, float2 *mm, cdn::QUpdate qu,
+           const float *__restrict__ ep_shift, float *__restrict__ out, cdn::QUpdate qu,
            int C, int ld_in, int ld_out, int Hs, int Ws, int relu, int nstrips, int rps) {
   extern __shared__ float4 ring4[];         // [RING][Ws + 2][LPP]
   constexpr int LPP = CCH / 4, RING = 3 + STRIDE, XPT = 256 / LPP;
@@ -381,9 +381,9 @@ dws_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, const u
       }
     }
   }
-  if (mm) {
+  if (qu.tracks()) {
     __syncthreads();
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), mm, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
                              reinterpret_cast<float *>(ring4));
   }
 }
@@ -402,7 +402,7 @@ template <bool XQ, int STRIDE, int MAXL>
 __global__ void __launch_bounds__(256)
 dwx_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, const unsigned char *__restrict__ agen,
            const float *__restrict__ w, const float *__restrict__ bias, const float *__restrict__ ep_scale,
-           const float *__restrict__ ep_shift, float *__restrict__ out, float2 *mm, cdn::QUpdate qu,
+           const float *__restrict__ ep_shift, float *__restrict__ out, cdn::QUpdate qu,
            int C, int ld_in, int ld_out, int Hs, int Ws, int relu, int nxs, int XSo, int nstrips, int rps,
            int LPP, int XPT) {
   extern __shared__ float4 ring4[];         // [RING][Wc][LPP]
@@ -583,9 +583,9 @@ dwx_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, const u
       }
     }
   }
-  if (mm) {
+  if (qu.tracks()) {
     __syncthreads();
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), mm, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
                              reinterpret_cast<float *>(ring4));
   }
 }
@@ -614,7 +614,7 @@ __global__ void __launch_bounds__(256)
 pwdwx_kernel(const float *__restrict__ x, const unsigned *__restrict__ xq, const signed char *__restrict__ Wq,
              const float *__restrict__ wscale, const int *__restrict__ wsum, const float *__restrict__ Wf,
              const float *__restrict__ pbias, const unsigned *__restrict__ mq, const float *__restrict__ w,
-             const float *__restrict__ bias, float *__restrict__ out, float2 *mm, cdn::QUpdate qu, int Cin, int Cpad,
+             const float *__restrict__ bias, float *__restrict__ out, cdn::QUpdate qu, int Cin, int Cpad,
              int C, int ld_x, int ld_out, int Hs, int Ws, int nxs, int XSo, int nstrips, int rps, int LPP, int XPT) {
   extern __shared__ float4 ring4[];         // [RING][Wc][LPP], then the code rows [2][Wc][24] dwords
   __shared__ unsigned s_wide_row[2];        // some code of the rows in flight does not fit int8 (-> nibble-split sums)
@@ -862,9 +862,9 @@ pwdwx_kernel(const float *__restrict__ x, const unsigned *__restrict__ xq, const
       }
     }
   }
-  if (mm) {
+  if (qu.tracks()) {
     __syncthreads();
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), mm, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
                              reinterpret_cast<float *>(ring4));
   }
 }
@@ -940,7 +940,7 @@ interleave_kernel(const float *__restrict__ srcA, int ldA, const unsigned *__res
 template <int CO>
 __global__ void __launch_bounds__(256)
 stem_kernel(const float *__restrict__ img, const float *__restrict__ w, const float *__restrict__ bias,
-            float *__restrict__ out, float2 *mm, cdn::QUpdate qu, int H, int W, int Ho, int Wo, int stride,
+            float *__restrict__ out, cdn::QUpdate qu, int H, int W, int Ho, int Wo, int stride,
             int relu) {
   __shared__ float red[16];
   const int n = blockIdx.y;
@@ -984,7 +984,7 @@ stem_kernel(const float *__restrict__ img, const float *__restrict__ w, const fl
       *reinterpret_cast<float4 *>(op + c4) = make_float4(r4[0], r4[1], r4[2], r4[3]);   // 96-byte pixel rows
     }
   }
-  if (mm) cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), mm, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu, red);
+  if (qu.tracks()) cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu, red);
 }
 
 constexpr int kHtLD = 48;      // bytes per A / B row of one 32-channel int8 k-step (32 + 16 pad): head_small_kernel
@@ -1053,7 +1053,7 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
                   const float *__restrict__ bdw, const unsigned *__restrict__ q2,
                   const signed char *__restrict__ Wq, const float *__restrict__ wscale,
                   const int *__restrict__ wsum, const float *__restrict__ bias, float *__restrict__ out,
-                  float2 *mm, cdn::QUpdate qu, int Hs, int Ws, int classes, int Cpad, int nxs, int XS,
+                  cdn::QUpdate qu, int Hs, int Ws, int classes, int Cpad, int nxs, int XS,
                   int nstrips, int rps, int only_if_wide, unsigned *oflow = nullptr) {
   // MODE 2 (up to 32 classes on the int8 matrix cores) handles codes that fit the nibble split; a batch with
   // wider codes (state[6], the first calls of a fresh running range) is left to the MODE 1 launch behind it
@@ -1369,9 +1369,9 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
     }
   }
   if (Y8 && MODE == 2 && clamped && oflow) atomicOr(oflow, 1u);
-  if (MODE == 0 && mm) {
+  if (MODE == 0 && qu.tracks()) {
     __syncthreads();
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), mm, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu,
                              reinterpret_cast<float *>(ring4));
   }
 }
@@ -1453,20 +1453,17 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
         int nstrips = (int)std::max<long>(1, std::min<long>(want, std::max(1, Ho_ / 8)));
         const int rps = (int)cdn::ceil_div(Ho_, nstrips);
         nstrips = (int)cdn::ceil_div(Ho_, rps);
-        if ((long)nstrips * nxs * N <= kMaxPartials) {
-          cdn::AuxWs ws{nullptr, nullptr};
-          if (r_state)
-            CDN_REQUIRE(cdn::aux_workspace(workspace, workspace_bytes, &ws), CDN_ERR_WORKSPACE,
-                        "workspace missing, too small or not 256-byte aligned");
+        if ((long)nstrips * nxs * N <= kMaxGrid) {
+          unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
+          CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
           hipStream_t st = cdn::as_stream(stream);
-          const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), ws.arrive,
+          const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
                                 (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
-          float2 *mm = r_state ? ws.partials : nullptr;
           const unsigned *aq = static_cast<const unsigned *>(a_qstate);
           dim3 grid((unsigned)(nstrips * nxs), (unsigned)N);
           cdn::ProfScope ps(cdn::kProfDw, (int)(H > 0xffff ? 0xffff : H), st);
 #define CDN_GOX(XQ_, ST_, ML_)                                                                          \
-  dwx_kernel<XQ_, ST_, ML_><<<grid, XPT * LPP, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, mm, \
+  dwx_kernel<XQ_, ST_, ML_><<<grid, XPT * LPP, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, \
       qu, (int)C, (int)ld_in, (int)ld_out, Hs, Ws, relu, nxs, XSo, nstrips, rps, LPP, XPT)
 #define CDN_GOX2(XQ_, ST_)                                                                              \
   do {                                                                                                  \
@@ -1503,15 +1500,12 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
       int nstrips = (int)std::max<long>(1, std::min<long>(want, std::max(1, Ho_ / 8)));
       const int rps = (int)cdn::ceil_div(Ho_, nstrips);
       nstrips = (int)cdn::ceil_div(Ho_, rps);
-      if ((long)nstrips * nchunks * N <= kMaxPartials && lds <= 64 * 1024) {
-        cdn::AuxWs ws{nullptr, nullptr};
-        if (r_state)
-          CDN_REQUIRE(cdn::aux_workspace(workspace, workspace_bytes, &ws), CDN_ERR_WORKSPACE,
-                      "workspace missing, too small or not 256-byte aligned");
+      if ((long)nstrips * nchunks * N <= kMaxGrid && lds <= 64 * 1024) {
+        unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
+        CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
         hipStream_t st = cdn::as_stream(stream);
-        const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), ws.arrive,
+        const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
                               (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
-        float2 *mm = r_state ? ws.partials : nullptr;
         const unsigned *aq = static_cast<const unsigned *>(a_qstate);
         dim3 grid((unsigned)(nstrips * nchunks), (unsigned)N);
         cdn::ProfScope ps(cdn::kProfDw, (int)(H > 0xffff ? 0xffff : H), st);
@@ -1519,13 +1513,13 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
 #define CDN_GOS(XQ_, ST_, CCH_)                                                                       \
   do {                                                                                                \
     if (maxl <= 1)                                                                                    \
-      dws_kernel<XQ_, ST_, CCH_, 1><<<grid, 256, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, mm, \
+      dws_kernel<XQ_, ST_, CCH_, 1><<<grid, 256, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, \
           qu, (int)C, (int)ld_in, (int)ld_out, Hs, Ws, relu, nstrips, rps);                           \
     else if (maxl == 2)                                                                               \
-      dws_kernel<XQ_, ST_, CCH_, 2><<<grid, 256, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, mm, \
+      dws_kernel<XQ_, ST_, CCH_, 2><<<grid, 256, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, \
           qu, (int)C, (int)ld_in, (int)ld_out, Hs, Ws, relu, nstrips, rps);                           \
     else                                                                                              \
-      dws_kernel<XQ_, ST_, CCH_, 4><<<grid, 256, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, mm, \
+      dws_kernel<XQ_, ST_, CCH_, 4><<<grid, 256, lds, st>>>(a, aq, a_gen, w, bias, ep_scale, ep_shift, out, \
           qu, (int)C, (int)ld_in, (int)ld_out, Hs, Ws, relu, nstrips, rps);                           \
   } while (0)
 #define CDN_GOS2(XQ_, ST_)                                                                            \
@@ -1552,15 +1546,12 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
   const size_t lds = (size_t)rows * (Ws + 2) * cch * sizeof(float);
   CDN_REQUIRE(lds <= 128 * 1024, CDN_ERR_UNSUPPORTED, "stored row of %d pixels too wide", Ws);
   const int nbands = (int)cdn::ceil_div(Hi, bandr), nchunks = (int)cdn::ceil_div(C, cch);
-  CDN_REQUIRE((long)nbands * nchunks * N <= kMaxPartials, CDN_ERR_UNSUPPORTED, "too many workgroups");
-  cdn::AuxWs ws{nullptr, nullptr};
-  if (r_state)
-    CDN_REQUIRE(cdn::aux_workspace(workspace, workspace_bytes, &ws), CDN_ERR_WORKSPACE,
-                "workspace missing, too small or not 256-byte aligned");
+  CDN_REQUIRE((long)nbands * nchunks * N <= kMaxGrid, CDN_ERR_UNSUPPORTED, "too many workgroups");
+  unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
+  CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
-  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), ws.arrive,
+  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
                         (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
-  float2 *mm = r_state ? ws.partials : nullptr;
   const unsigned *aq = static_cast<const unsigned *>(a_qstate);
   dim3 grid((unsigned)(nbands * nchunks), (unsigned)N);
   cdn::ProfScope ps(cdn::kProfDw, (int)(H > 0xffff ? 0xffff : H), st);
@@ -1569,7 +1560,7 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
     auto kern = cch == 32 ? dw3_kernel<XQ_, UP_, ST_, 32> : dw3_kernel<XQ_, UP_, ST_, 16>;         \
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,      \
                               (int)lds);                                                           \
-    kern<<<grid, 256, lds, st>>>(a, aq, w, bias, ep_scale, ep_shift, out, mm, qu, (int)C, (int)ld_in, \
+    kern<<<grid, 256, lds, st>>>(a, aq, w, bias, ep_scale, ep_shift, out, qu, (int)C, (int)ld_in, \
                                  (int)ld_out, Hs, Ws, relu, nbands, a_gen);                        \
   }
   if (aq && up) CDN_GO(true, 1, 1)
@@ -1614,15 +1605,13 @@ extern "C" int cdn_codenet_stem_forward(const float *img, int64_t N, int64_t H, 
               CDN_ERR_ARG, "the output QuantAct needs x_min, x_max and state together");
   const int Ho = (int)((H + 2 - 3) / stride + 1), Wo = (int)((W + 2 - 3) / stride + 1);
   dim3 grid((unsigned)cdn::ceil_div((long)Ho * Wo, 256), (unsigned)N);
-  CDN_REQUIRE(N <= 65535 && (long)grid.x * grid.y <= kMaxPartials, CDN_ERR_UNSUPPORTED, "too many workgroups");
-  cdn::AuxWs ws{nullptr, nullptr};
-  if (r_state)
-    CDN_REQUIRE(cdn::aux_workspace(workspace, workspace_bytes, &ws), CDN_ERR_WORKSPACE,
-                "workspace missing, too small or not 256-byte aligned");
+  CDN_REQUIRE(N <= 65535 && (long)grid.x * grid.y <= kMaxGrid, CDN_ERR_UNSUPPORTED, "too many workgroups");
+  unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
+  CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
-  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), ws.arrive,
+  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
                         (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
-  stem_kernel<24><<<grid, 256, 0, st>>>(img, w, bias, out, r_state ? ws.partials : nullptr, qu, (int)H,
+  stem_kernel<24><<<grid, 256, 0, st>>>(img, w, bias, out, qu, (int)H,
                                         (int)W, Ho, Wo, stride, relu);
   return cdn::check_launch("codenet stem");
 }
@@ -1658,7 +1647,7 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
     *nstrips = (int)cdn::ceil_div(Hs, *rps);
     *lds = (size_t)4 * (XS + 2) * 16 * 16;
     *grid = dim3((unsigned)(*nstrips * *nxs), (unsigned)N);
-    return (long)*nstrips * *nxs * N <= kMaxPartials;
+    return (long)*nstrips * *nxs * N <= kMaxGrid;
   };
   int nxs, nstrips, rps;
   size_t lds;
@@ -1668,13 +1657,12 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
   cdn::ProfScope ps(cdn::kProfDw, (int)Hs, st);
   if (mode == 0) {
     CDN_REQUIRE(r_min && r_max && r_state, CDN_ERR_ARG, "the range pass needs x_min, x_max and state");
-    cdn::AuxWs ws{nullptr, nullptr};
-    CDN_REQUIRE(cdn::aux_workspace(workspace, workspace_bytes, &ws), CDN_ERR_WORKSPACE,
-                "workspace missing, too small or not 256-byte aligned");
-    const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), ws.arrive,
+    unsigned *arrive = cdn::aux_workspace(workspace, workspace_bytes);
+    CDN_REQUIRE(arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
+    const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
                           (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
     head_small_kernel<0, 2><<<grid, 256, lds, st>>>(y1, q1, w_dw, b_dw, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                    nullptr, ws.partials, qu, (int)Hs, (int)Ws, 0, 0, nxs, XS, nstrips,
+                                                    nullptr, qu, (int)Hs, (int)Ws, 0, 0, nxs, XS, nstrips,
                                                     rps, 0);
     return cdn::check_launch("codenet head range");
   }
@@ -1694,13 +1682,13 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
     if (mfma_ok) {
     } else if (classes <= 2) {
       head_small_kernel<1, 2, Y8><<<grid, 256, lds, st>>>(y1, q1, w_dw, b_dw, q2, w_codes, w_scale, nullptr, bias,
-                                                          out_nchw, nullptr, none, (int)Hs, (int)Ws, (int)classes, Cpad,
+                                                          out_nchw, none, (int)Hs, (int)Ws, (int)classes, Cpad,
                                                           nxs, XS, nstrips, rps, 0);
       return cdn::check_launch("codenet head tail (small)");
     }
     if (classes <= 4 && !mfma_ok) {
       head_small_kernel<1, 4, Y8><<<grid, 256, lds, st>>>(y1, q1, w_dw, b_dw, q2, w_codes, w_scale, nullptr, bias,
-                                                          out_nchw, nullptr, none, (int)Hs, (int)Ws, (int)classes, Cpad,
+                                                          out_nchw, none, (int)Hs, (int)Ws, (int)classes, Cpad,
                                                           nxs, XS, nstrips, rps, 0);
       return cdn::check_launch("codenet head tail (small)");
     }
@@ -1715,7 +1703,7 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
       CDN_REQUIRE(geom(16, &nxs2, &nstrips2, &rps2, &lds2, &grid2), CDN_ERR_UNSUPPORTED, "too many workgroups");
       lds2 += (size_t)2 * 2 * (4 * 16) * kHtLD + (size_t)2 * 2 * 32 * kHtLD;
       head_small_kernel<2, 2, Y8><<<grid2, 256, lds2, st>>>(y1, q1, w_dw, b_dw, q2, w_codes, w_scale, w_colsum, bias,
-                                                            out_nchw, nullptr, none, (int)Hs, (int)Ws, (int)classes,
+                                                            out_nchw, none, (int)Hs, (int)Ws, (int)classes,
                                                             Cpad, nxs2, 16, nstrips2, rps2, 0, overflow);
     }
     // the wide-code fallback behind it -- never on byte-code input: frozen ranges have no wide batches (state[6] is 0 by
@@ -1723,7 +1711,7 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
     // head in the serving network's kernel trace
     if (!Y8)
       head_small_kernel<1, 4, Y8><<<grid, 256, lds, st>>>(y1, q1, w_dw, b_dw, q2, w_codes, w_scale, nullptr, bias,
-                                                          out_nchw, nullptr, none, (int)Hs, (int)Ws, (int)classes, Cpad,
+                                                          out_nchw, none, (int)Hs, (int)Ws, (int)classes, Cpad,
                                                           nxs, XS, nstrips, rps, 1);
     return cdn::check_launch("codenet head tail (matrix cores)");
   };
@@ -1847,20 +1835,17 @@ static int pwdw_s2_impl(
   int nstrips = (int)std::max<long>(1, std::min<long>(want, std::max(1, Ho / 8)));
   const int rps = (int)cdn::ceil_div(Ho, nstrips);
   nstrips = (int)cdn::ceil_div(Ho, rps);
-  CDN_REQUIRE((long)nstrips * nxs * N <= kMaxPartials, CDN_ERR_UNSUPPORTED, "too many workgroups");
-  cdn::AuxWs ws{nullptr, nullptr};
-  if (r_state)
-    CDN_REQUIRE(cdn::aux_workspace(workspace, workspace_bytes, &ws), CDN_ERR_WORKSPACE,
-                "workspace missing, too small or not 256-byte aligned");
+  CDN_REQUIRE((long)nstrips * nxs * N <= kMaxGrid, CDN_ERR_UNSUPPORTED, "too many workgroups");
+  unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
+  CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
-  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), ws.arrive, (float)(momentum - 1.0),
+  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive, (float)(momentum - 1.0),
                         (float)(1.0 - momentum), bits, running};
-  float2 *mm = r_state ? ws.partials : nullptr;
   const int Cpad = (int)((Cin + 63) / 64 * 64);
   dim3 grid((unsigned)(nstrips * nxs), (unsigned)N);
 #define CDN_GOPD1(ML_, Q_)                                                                                     \
   pwdwx_kernel<ML_, Q_><<<grid, XPT * LPP, lds, st>>>(x, static_cast<const unsigned *>(x_qstate), w_pw_codes, w_pw_scale, \
-      w_pw_colsum, w_pw, bias_pw, static_cast<const unsigned *>(m_state), w_dw, bias_dw, out, mm, qu, (int)Cin, Cpad, \
+      w_pw_colsum, w_pw, bias_pw, static_cast<const unsigned *>(m_state), w_dw, bias_dw, out, qu, (int)Cin, Cpad, \
       (int)C, (int)ld_x, (int)ld_out, Hs, Ws, nxs, XSo, nstrips, rps, LPP, XPT)
 #define CDN_GOPD(ML_)                  \
   do {                                 \

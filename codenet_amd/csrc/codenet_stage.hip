@@ -120,7 +120,7 @@ scale_kernel(const float *__restrict__ x, const float *__restrict__ w,
   // inference schedule does: no update launch behind this kernel)
   if (qu.counters) {
     __syncthreads();
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), nullptr, blockIdx.y * gridDim.x + blockIdx.x,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x,
                              gridDim.x * gridDim.y, qu, &red[0][0]);
     cdn::last_block_state_copy(qu, state_copy, &red[0][0]);
   } else if (mm) {
@@ -338,7 +338,7 @@ dw4_kernel(const float *__restrict__ x, const float *__restrict__ s, const float
     }
   }
   if (qu.counters) {
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), nullptr, blockIdx.y * gridDim.x + blockIdx.x,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x,
                              gridDim.x * gridDim.y, qu, red_mm);
     cdn::last_block_state_copy(qu, state_copy, red_mm);
   } else if (mm) cdn::block_minmax_store(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), &mm[blockIdx.y * gridDim.x + blockIdx.x], red_mm);

@@ -1108,7 +1108,7 @@ pwi8n_kernel(const float *__restrict__ D, const unsigned *__restrict__ dq, const
       mx = cdn::relu_keep_nan(mx);
     }
     __syncthreads();
-    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), nullptr, blockIdx.y * gridDim.x + blockIdx.x,
+    cdn::block_minmax_finish(cdn::nan_lo(mn, has_nan), cdn::nan_hi(mx, has_nan), blockIdx.y * gridDim.x + blockIdx.x,
                              gridDim.x * gridDim.y, qu, reinterpret_cast<float *>(pwn_lds));
   } else if (mm) {
     __syncthreads();

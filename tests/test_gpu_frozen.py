@@ -102,6 +102,34 @@ def test_frozen_overflow_flag_when_codes_leave_the_grid():
         assert f2.overflowed(), which
 
 
+@pytest.mark.parametrize("planes,res,stage", [([64, 32, 16, 8], 8, 0), ([128, 64, 32, 16], 8, 1)])
+def test_frozen_gather_alone_raises_the_overflow_word_of_its_stage(planes, res, stage):
+    """The byte-output gathers report a saturated code of d through their own overflow argument: dw2_kernel (stage 0:
+    NCHW input, 64 -> 32 channels on an 8 x 8 plane) and dw2u_kernel (stage 1 behind a 128 -> 64 stage: up-sampled input, 64 -> 32 channels, 8 x 8
+    stored, 16 x 16 plane).  Only the gather's quantiser of that stage is shrunk, and the stage's output range is widened
+    tenfold so that its pointwise launch cannot saturate: the stage's word can only come from the gather, and the words
+    of the stages in front of it stay clean."""
+    from codenet_amd import pipeline
+    from codenet_amd.pipeline.hotpath import stage_acts
+    net = pipeline.build_hot_path(quantized=True, planes=planes, seed=44).cuda()
+    xs = _inputs(2, planes[0], res, 1, 144)
+    _warm_and_freeze(net, xs)
+    frz = pipeline.FrozenHotPath(net.deconv_layers)
+    frz(xs[0].cuda())
+    assert not frz.overflowed()
+    _, d_act, r_act = stage_acts(frz.stages[stage])
+    with torch.no_grad():
+        for act, f in ((d_act, 0.4), (r_act, 10.0)):
+            mid, half = (act.x_max + act.x_min) / 2, (act.x_max - act.x_min) / 2
+            act.x_min.copy_(mid - f * half)
+            act.x_max.copy_(mid + f * half)
+    frz(xs[0].cuda())
+    words = frz._bufs["overflow"].words.tolist()
+    assert words[stage] != 0 and not any(words[:stage]), words
+    assert d_act in frz._bufs["overflow"].acts(reset=False)
+    assert frz.overflowed() and not frz.overflowed()
+
+
 def test_frozen_nhwc_input_with_quantiser_state():
     """Stage 0 fed by a native backbone: channels-last pre-quantisation values + their QuantAct state."""
     from codenet_amd import pipeline

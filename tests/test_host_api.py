@@ -68,6 +68,10 @@ def test_argument_validation_of_the_layer_entry_points_without_gpu():
     lib = _native.lib()
     one = 4096
     assert lib.cdn_codenet_aux_workspace_bytes() >= 16384 * 8
+    # ABI 1 pins the workspace sizes (the reserved regions that once held {min, max} partials included)
+    assert lib.cdn_codenet_aux_workspace_bytes() == 135424
+    assert lib.cdn_codenet_stage_workspace_bytes(64, 1024, 16, 16, 0) == 67613440
+    assert lib.cdn_codenet_stage_workspace_bytes(32, 256, 32, 32, 1) == 34026240
     # pointwise: output QuantAct given without a workspace
     rc = lib.cdn_codenet_pointwise_nhwc_forward(one, None, 64, 16, 16, 0, 0, one, None, None, None, None,
                                                 None, None, 1, one, one, one, 8, 0.99, 1, None, 0, one, None)

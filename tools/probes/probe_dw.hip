@@ -40,7 +40,7 @@ static float time_us(F launch, int iters = 20) {
 
 int main() {
   const int N = 64;
-  float *x, *s_raw, *wd, *d, *xmin, *xmax; float2 *mm; unsigned *state, *sstate, *xstate, *counters;
+  float *x, *s_raw, *wd, *d, *xmin, *xmax; unsigned *state, *sstate, *xstate, *counters;
   (void)hipMalloc(&x, (size_t)N * 1024 * 256 * 4);
   {
     std::vector<float> hx((size_t)N * 1024 * 256);
@@ -61,7 +61,6 @@ int main() {
   }
   (void)hipMemcpy(s_raw, ones.data(), ones.size() * 4, hipMemcpyHostToDevice);
   (void)hipMalloc(&wd, 1024 * 9 * 4); (void)hipMemset(wd, 0, 1024 * 9 * 4);
-  (void)hipMalloc(&mm, 16384 * 8);
   (void)hipMalloc(&xmin, 4); (void)hipMalloc(&xmax, 4); (void)hipMalloc(&state, 64); (void)hipMalloc(&sstate, 64); (void)hipMalloc(&xstate, 64);
   (void)hipMalloc(&counters, cdn::kArriveWords * 4);
   (void)hipMemset(xmin, 0, 4); (void)hipMemset(xmax, 0, 4); (void)hipMemset(state, 0, 64); (void)hipMemset(counters, 0, cdn::kArriveWords * 4);
@@ -70,19 +69,19 @@ int main() {
   cdn::QUpdate qu{xmin, xmax, state, counters, -0.01f, 0.01f, 8, 1};
   // stage 0: C=1024, 16x16, NCHW, up=0
   {
-    auto run = [&] { launch_dw2<64>(false, x, nullptr, s_raw, sstate, wd, d, mm, qu, N, 1024, 16, 16, 0, nullptr); };
+    auto run = [&] { launch_dw2<64>(false, x, nullptr, s_raw, sstate, wd, d, qu, N, 1024, 16, 16, 0, nullptr); };
     float us = time_us(run); run(); (void)hipDeviceSynchronize();
     report("stage0 dw2<64> 16x16", 16 * N, us);
   }
   // stage 1: C=256, 32x32 from 16x16 NHWC, up=1  -> dw2u<64>
   {
-    auto run = [&] { launch_dw2<64>(true, x, xstate, s_raw, sstate, wd, d, mm, qu, N, 256, 32, 32, 1, nullptr); };
+    auto run = [&] { launch_dw2<64>(true, x, xstate, s_raw, sstate, wd, d, qu, N, 256, 32, 32, 1, nullptr); };
     float us = time_us(run); run(); (void)hipDeviceSynchronize();
     report("stage1 dw2u<64> 32x32", 4 * N, us);
   }
   // stage 2: C=128, 64x64 from 32x32 NHWC, up=1 -> dw2u<32>
   {
-    auto run = [&] { launch_dw2<32>(true, x, xstate, s_raw, sstate, wd, d, mm, qu, N, 128, 64, 64, 1, nullptr); };
+    auto run = [&] { launch_dw2<32>(true, x, xstate, s_raw, sstate, wd, d, qu, N, 128, 64, 64, 1, nullptr); };
     float us = time_us(run); run(); (void)hipDeviceSynchronize();
     report("stage2 dw2u<32> 64x64", 4 * N, us);
   }

@@ -9,7 +9,7 @@ constexpr int N = 64, C = 1024, HW = 256;
 // MODE 0: loads only; 1: + weights/fma; 2: + LDS reduce + store s; 3: + block_minmax_finish
 template <int MODE>
 __global__ void __launch_bounds__(1024) k(const float *__restrict__ x, const float *__restrict__ w,
-                                          float *__restrict__ s, float2 *mm, cdn::QUpdate qu) {
+                                          float *__restrict__ s, cdn::QUpdate qu) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int p = blockIdx.x * 64 + lane, n = blockIdx.y;
   const float *xp = x + (long)n * C * HW + p;
@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(1024) k(const float *__restrict__ x, const flo
       mn = mx = v;
     }
   } else if (a == 12345.f) s[0] = a;
-  if (MODE >= 3) cdn::block_minmax_finish(mn, mx, mm, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu, &red[0][0]);
+  if (MODE >= 3) cdn::block_minmax_finish(mn, mx, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, qu, &red[0][0]);
 }
 template <typename F>
 float timeit(F launch, int iters = 40) {
@@ -57,19 +57,19 @@ int main() {
   unsigned u = 12345u;
   for (auto &v : hx) { u = u * 1664525u + 1013904223u; v = rnd ? (float)(u >> 8) * (1.0f / 16777216.0f) : 0.f; }
   for (auto &b : bufs) { (void)hipMalloc(&b, n * 4); (void)hipMemcpy(b, hx.data(), n * 4, hipMemcpyHostToDevice); }
-  float *w, *s, *xmin, *xmax; float2 *mm; unsigned *state, *counters;
+  float *w, *s, *xmin, *xmax; unsigned *state, *counters;
   (void)hipMalloc(&w, C * 4); (void)hipMemset(w, 0, C * 4);
-  (void)hipMalloc(&s, N * HW * 4); (void)hipMalloc(&mm, 16384 * 8);
+  (void)hipMalloc(&s, N * HW * 4);
   (void)hipMalloc(&xmin, 4); (void)hipMalloc(&xmax, 4); (void)hipMalloc(&state, 64); (void)hipMalloc(&counters, cdn::kArriveWords * 4);
   (void)hipMemset(xmin, 0, 4); (void)hipMemset(xmax, 0, 4); (void)hipMemset(state, 0, 64); (void)hipMemset(counters, 0, cdn::kArriveWords * 4);
   cdn::QUpdate qu{xmin, xmax, state, counters, -0.01f, 0.01f, 8, 1};
   const double mb = n * 4 / 1e6;
   auto rep = [&](const char *name, float us) { printf("%-34s %7.1f us  %6.2f TB/s\n", name, us, mb / us / 1e6); };
   dim3 g(4, N);
-  rep("0 loads only", timeit([&](int i) { k<0><<<g, 1024>>>(bufs[i & 7], w, s, mm, qu); }));
-  rep("1 + weights/fma", timeit([&](int i) { k<1><<<g, 1024>>>(bufs[i & 7], w, s, mm, qu); }));
-  rep("2 + LDS reduce + store", timeit([&](int i) { k<2><<<g, 1024>>>(bufs[i & 7], w, s, mm, qu); }));
-  rep("3 + minmax finish", timeit([&](int i) { k<3><<<g, 1024>>>(bufs[i & 7], w, s, mm, qu); }));
-  rep("3 same buffer", timeit([&](int i) { k<3><<<g, 1024>>>(bufs[0], w, s, mm, qu); }));
+  rep("0 loads only", timeit([&](int i) { k<0><<<g, 1024>>>(bufs[i & 7], w, s, qu); }));
+  rep("1 + weights/fma", timeit([&](int i) { k<1><<<g, 1024>>>(bufs[i & 7], w, s, qu); }));
+  rep("2 + LDS reduce + store", timeit([&](int i) { k<2><<<g, 1024>>>(bufs[i & 7], w, s, qu); }));
+  rep("3 + minmax finish", timeit([&](int i) { k<3><<<g, 1024>>>(bufs[i & 7], w, s, qu); }));
+  rep("3 same buffer", timeit([&](int i) { k<3><<<g, 1024>>>(bufs[0], w, s, qu); }));
   return 0;
 }
