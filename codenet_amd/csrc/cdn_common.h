@@ -276,6 +276,16 @@ struct QUpdate {
   // this launch measures its output's range: the producer ends with block_minmax_finish
   __host__ __device__ bool tracks() const { return counters != nullptr; }
 };
+// The QUpdate of a QuantAct as the entry points receive it.  Python evaluates (momentum - 1.) and (1. - momentum) in
+// double, then the tensor op rounds the scalar to fp32 (quant_modules.py:217-219): the pair below, and nothing computed
+// from a float momentum, makes the range EMA bit-exact.
+inline QUpdate make_qupdate(float *x_min, float *x_max, void *state, unsigned *counters, int bits, double momentum,
+                            int running) {
+  return QUpdate{x_min, x_max, static_cast<unsigned *>(state), counters, (float)(momentum - 1.0), (float)(1.0 - momentum),
+                 bits, running};
+}
+// no QuantAct behind this launch: nothing is measured, nothing updated
+inline QUpdate no_qupdate() { return QUpdate{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 8, 0}; }
 // Arrival counters: 64 group counters + 1 top counter, one per 64-byte line (a single contended
 // word sustains only ~88 atomics/us; 2048 workgroups on one word cost ~25 us).
 constexpr int kArriveGroups = 64;
@@ -484,6 +494,47 @@ int launch_frozen_dw(const void *x, int x_kind, const unsigned *xq, const float 
 size_t aux_workspace_bytes();
 unsigned *aux_workspace(void *workspace, size_t bytes);
 }  // namespace cdn
+
+#ifdef __HIPCC__
+namespace cdn {
+// codenet_pointwise.hip, shared with the stage schedule (codenet_fused.hip).  One pointwise (1x1) convolution
+// A [M][C] -> R [M][Co] on channels-last rows; the operands given decide the kernel family (launch_pointwise).
+struct PwCall {
+  const float *a;               // A: fp32 rows (pre-quantisation values when a_state is given)
+  unsigned *a_state;            // QuantAct state of A (the int8 kernels derive the codes from it) or NULL: final values
+  long M;
+  int64_t C, Co;
+  const float *w;               // fp32 weights [Co][C]
+  const signed char *w_codes;   // their 4-bit codes + w_scale [Co] + w_colsum [Co], or NULL
+  const float *w_scale;
+  const int *w_colsum;
+  const float *bias, *ep_scale, *ep_shift;      // bias [Co] or NULL; affine epilogue (BN), both or neither
+  int relu;
+  float *out;                   // R (NULL: range-only pass of the int8 kernel)
+  QUpdate qu;                   // QuantAct behind R; measured iff qu.tracks()
+  int ptag;                     // tag of the ProfScope
+  hipStream_t st;
+  int64_t lda = 0, ldo = 0;     // row strides of A / R in floats (views into wider channels-last tensors); 0: dense
+  const unsigned char *a_gen = nullptr;   // mixed-generation input: per channel, which state of a_state applies
+  const int *out_map = nullptr;           // output channel map (needs the 4-bit weight codes)
+  // the rows of A hold lda = round_up(C, 64) valid floats (the pad repeats channel C - 1) and the weight codes are zero
+  // beyond C: the int8 path runs its whole-tile form over K = lda; the f32 branch for wide codes keeps C
+  bool a_padded = false;
+  const signed char *w_kb = nullptr;      // the k-blocked copy of w_codes (include/codenet_dcn.h, CDN_X_WCODES_KB) or NULL
+  // chained fp32 stages (pws_kernel only; the caller asked cdn_codenet_stage_chain_parts first)
+  const float *next_ws = nullptr;
+  float *sparts = nullptr;
+  int n_gens = 0;               // how many states a_gen can name (0: unknown) -- pwd3_kernel then loads them all at once
+};
+int launch_pointwise(const PwCall &p);
+int pointwise_chain_parts(long M, int64_t C, int64_t Co);
+#ifdef CDN_STAMPS
+// region 2 of the in-kernel phase stamps (2048 workgroups x 8 stamps) lives beside the kernels that write it
+int read_pointwise_stamps(unsigned long long *host_dst);
+int clear_pointwise_stamps();
+#endif
+}  // namespace cdn
+#endif
 
 #define CDN_REQUIRE(cond, code, ...) \
   do {                               \

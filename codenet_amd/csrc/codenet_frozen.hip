@@ -670,10 +670,18 @@ extern "C" int cdn_quantact_frozen_params_clear(int n, float *const *x_min, floa
   return frozen_params_impl(n, x_min, x_max, state, bits, clear, clear_bytes, stream);
 }
 
-extern "C" size_t cdn_codenet_stage_frozen_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int x_up) {
+// workspace of the frozen stage: s_raw (fp32, stored resolution) at byte 0, then d (byte codes), each rounded up to 256 bytes
+struct FrozenWorkspace {
+  int64_t d8, bytes;
+};
+static FrozenWorkspace frozen_workspace(int64_t N, int64_t C, int64_t H, int64_t W, int x_up) {
   const int64_t HWl = (H >> x_up) * (W >> x_up);
   auto r = [](int64_t b) { return (b + 255) / 256 * 256; };
-  return (size_t)(r(N * HWl * 4) + r(N * H * W * C));        // s_raw (fp32) + d (byte codes)
+  return FrozenWorkspace{r(N * HWl * 4), r(N * HWl * 4) + r(N * H * W * C)};
+}
+
+extern "C" size_t cdn_codenet_stage_frozen_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int x_up) {
+  return (size_t)frozen_workspace(N, C, H, W, x_up).bytes;
 }
 
 static int pointwise_q8_impl(const signed char *a, const void *a_state, int64_t M, int64_t C,
@@ -760,9 +768,8 @@ static int stage_frozen_impl(
               CDN_ERR_ARG, "x / r8_out must be 16-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
   const int64_t HWl = (H >> x_up) * (W >> x_up);
-  auto r256 = [](int64_t b) { return (b + 255) / 256 * 256; };
   float *s_raw = static_cast<float *>(workspace);
-  signed char *d8 = static_cast<signed char *>(workspace) + r256(N * HWl * 4);
+  signed char *d8 = static_cast<signed char *>(workspace) + frozen_workspace(N, C, H, W, x_up).d8;
   const unsigned *xq = static_cast<const unsigned *>(x_state);
   const int ptag = (int)(H > 0xffff ? 0xffff : H);
   int rc = 0;

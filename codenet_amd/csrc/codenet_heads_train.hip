@@ -363,12 +363,11 @@ extern "C" int cdn_codenet_head_dw_forward(const float *y1, const void *a1_state
   CDN_REQUIRE(y1 && a1_state && w2 && r2, CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, CDN_ERR_ARG, "non-positive size");
   CDN_REQUIRE(N * C * H * W < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
-  cdn::QUpdate qu{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 8, 0};
+  cdn::QUpdate qu = cdn::no_qupdate();
   if (running) {
     CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");
     CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
-    qu = cdn::QUpdate{x_min, x_max, static_cast<unsigned *>(state), static_cast<unsigned *>(counters),
-                      (float)(momentum - 1.0), (float)(1.0 - momentum), bits, 1};
+    qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
   }
   const HdPlan p = head_plan(H, W);
   const long items = (long)(N * C) * p.strips * p.wq;

@@ -5,7 +5,7 @@
 //                      (detection heads: SURVEY.md section 8f row 1; ShuffleNetV2 units: row 3)
 //   interleave_kernel  concat + channel_shuffle(2) + the shared block-output QuantAct of a unit
 //   stem_kernel        layer0: dense 3x3 conv 3 -> 24 on the NCHW image
-// The pointwise convolutions of these layers are the stage's pointwise kernels (codenet_fused.hip,
+// The pointwise convolutions of these layers are the stage's pointwise kernels (codenet_pointwise.hip,
 // cdn_codenet_pointwise_nhwc_forward).
 #include "cdn_common.h"
 
@@ -1457,8 +1457,7 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
           unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
           CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
           hipStream_t st = cdn::as_stream(stream);
-          const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
-                                (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
+          const cdn::QUpdate qu = cdn::make_qupdate(r_min, r_max, r_state, arrive, bits, momentum, running);
           const unsigned *aq = static_cast<const unsigned *>(a_qstate);
           dim3 grid((unsigned)(nstrips * nxs), (unsigned)N);
           cdn::ProfScope ps(cdn::kProfDw, (int)(H > 0xffff ? 0xffff : H), st);
@@ -1504,8 +1503,7 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
         unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
         CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
         hipStream_t st = cdn::as_stream(stream);
-        const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
-                              (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
+        const cdn::QUpdate qu = cdn::make_qupdate(r_min, r_max, r_state, arrive, bits, momentum, running);
         const unsigned *aq = static_cast<const unsigned *>(a_qstate);
         dim3 grid((unsigned)(nstrips * nchunks), (unsigned)N);
         cdn::ProfScope ps(cdn::kProfDw, (int)(H > 0xffff ? 0xffff : H), st);
@@ -1550,8 +1548,7 @@ extern "C" int cdn_codenet_dw3x3_mixed_forward(
   unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
   CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
-  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
-                        (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
+  const cdn::QUpdate qu = cdn::make_qupdate(r_min, r_max, r_state, arrive, bits, momentum, running);
   const unsigned *aq = static_cast<const unsigned *>(a_qstate);
   dim3 grid((unsigned)(nbands * nchunks), (unsigned)N);
   cdn::ProfScope ps(cdn::kProfDw, (int)(H > 0xffff ? 0xffff : H), st);
@@ -1609,8 +1606,7 @@ extern "C" int cdn_codenet_stem_forward(const float *img, int64_t N, int64_t H, 
   unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
   CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
-  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
-                        (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
+  const cdn::QUpdate qu = cdn::make_qupdate(r_min, r_max, r_state, arrive, bits, momentum, running);
   stem_kernel<24><<<grid, 256, 0, st>>>(img, w, bias, out, qu, (int)H,
                                         (int)W, Ho, Wo, stride, relu);
   return cdn::check_launch("codenet stem");
@@ -1659,8 +1655,7 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
     CDN_REQUIRE(r_min && r_max && r_state, CDN_ERR_ARG, "the range pass needs x_min, x_max and state");
     unsigned *arrive = cdn::aux_workspace(workspace, workspace_bytes);
     CDN_REQUIRE(arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
-    const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive,
-                          (float)(momentum - 1.0), (float)(1.0 - momentum), bits, running};
+    const cdn::QUpdate qu = cdn::make_qupdate(r_min, r_max, r_state, arrive, bits, momentum, running);
     head_small_kernel<0, 2><<<grid, 256, lds, st>>>(y1, q1, w_dw, b_dw, nullptr, nullptr, nullptr, nullptr, nullptr,
                                                     nullptr, qu, (int)Hs, (int)Ws, 0, 0, nxs, XS, nstrips,
                                                     rps, 0);
@@ -1670,7 +1665,7 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
   CDN_REQUIRE(classes >= 1 && classes <= 32, CDN_ERR_UNSUPPORTED, "head tail handles 1..32 output channels");
   CDN_REQUIRE((reinterpret_cast<uintptr_t>(w_codes) & 15) == 0, CDN_ERR_ARG, "w_codes must be 16-byte aligned");
   const int Cpad = (int)((C + 63) / 64 * 64);
-  const cdn::QUpdate none{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 8, 0};
+  const cdn::QUpdate none = cdn::no_qupdate();
   const unsigned *q2 = static_cast<const unsigned *>(y2_qstate);
   // matrix cores whenever the shape allows (measured at 2 classes: 64 us vs 74 us for the VALU form, which
   // remains for other widths and as the wide-code fallback)
@@ -1839,8 +1834,7 @@ static int pwdw_s2_impl(
   unsigned *arrive = r_state ? cdn::aux_workspace(workspace, workspace_bytes) : nullptr;
   CDN_REQUIRE(!r_state || arrive, CDN_ERR_WORKSPACE, "workspace missing, too small or not 256-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
-  const cdn::QUpdate qu{r_min, r_max, static_cast<unsigned *>(r_state), arrive, (float)(momentum - 1.0),
-                        (float)(1.0 - momentum), bits, running};
+  const cdn::QUpdate qu = cdn::make_qupdate(r_min, r_max, r_state, arrive, bits, momentum, running);
   const int Cpad = (int)((Cin + 63) / 64 * 64);
   dim3 grid((unsigned)(nstrips * nxs), (unsigned)N);
 #define CDN_GOPD1(ML_, Q_)                                                                                     \

@@ -387,12 +387,10 @@ namespace cdn {
 void launch_quantact_update(float *x_min, float *x_max, unsigned *state, const float *ext_min,
                             const float *ext_max, const float2 *partials, int n_partials, int bits,
                             double momentum, int running, hipStream_t st, int relu, unsigned *state_copy) {
-  // Python evaluates (momentum - 1.) and (1. - momentum) in double, then the tensor op rounds
-  // the scalar to fp32 (quant_modules.py:217-219).
+  const QUpdate u = make_qupdate(x_min, x_max, state, nullptr, bits, momentum, running);      // (for its momentum pair)
   const int threads = (!ext_min && partials) ? 256 : 64;
-  quantact_update_kernel<<<1, threads, 0, st>>>(x_min, x_max, state, ext_min, ext_max, partials,
-                                                n_partials, bits, (float)(momentum - 1.0),
-                                                (float)(1.0 - momentum), running, relu, state_copy);
+  quantact_update_kernel<<<1, threads, 0, st>>>(x_min, x_max, state, ext_min, ext_max, partials, n_partials, bits,
+                                                u.m_minus_1, u.one_minus_m, running, relu, state_copy);
 }
 }  // namespace cdn
 
@@ -414,7 +412,7 @@ extern "C" int cdn_quantact_forward(const float *x, float *out, int16_t *codes, 
   hipStream_t st = cdn::as_stream(stream);
   unsigned *stt = static_cast<unsigned *>(state);
   if (running && !batch_min) {     // range pass + update in one launch (the last workgroup updates)
-    const cdn::QUpdate qu{x_min, x_max, stt, nullptr, (float)(momentum - 1.0), (float)(1.0 - momentum), bits, 1};
+    const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, stt, nullptr, bits, momentum, 1);
     minmax_kernel<false><<<minmax_grid(numel), 256, 0, st>>>(x, (long)numel, qu);
   } else {
     cdn::launch_quantact_update(x_min, x_max, stt, batch_min, batch_max, nullptr, 0, bits, momentum,
@@ -487,7 +485,7 @@ static int relu_up2_impl(const float *y, float *out, int64_t planes, int64_t H, 
     cdn::launch_quantact_update(x_min, x_max, stt, nullptr, nullptr, reinterpret_cast<const float2 *>(partials),
                                 (int)n_partials, bits, momentum, running, st, 1);
   } else if (running) {
-    const cdn::QUpdate qu{x_min, x_max, stt, nullptr, (float)(momentum - 1.0), (float)(1.0 - momentum), bits, 1};
+    const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, stt, nullptr, bits, momentum, 1);
     minmax_kernel<true><<<minmax_grid(numel), 256, 0, st>>>(y, numel, qu);
   } else {
     cdn::launch_quantact_update(x_min, x_max, stt, nullptr, nullptr, nullptr, 0, bits, momentum, running, st);

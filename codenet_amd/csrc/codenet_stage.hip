@@ -1221,7 +1221,7 @@ pointwise_kernel(const float *__restrict__ D, const float *__restrict__ Wp,
 // The three forward kernels of the stage optionally leave one {min, max} pair per workgroup of the tensor they wrote
 // (`partials`, *_range_partials(...) float2 entries): the training path's QuantAct behind them reduces those instead of
 // re-reading the tensor (cdn_quantact_forward_partials / cdn_quantact_relu_up2_forward_partials).
-static const cdn::QUpdate kNoUpdate{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 8, 0};
+static const cdn::QUpdate kNoUpdate = cdn::no_qupdate();
 
 // qu (round 6): the QuantAct behind the kernel, updated by its last workgroup (cdn_codenet_*_forward_update)
 static int scale_forward_impl(const float *x, const float *w_scale, const float *b_scale, float *s, int64_t N,
@@ -1509,10 +1509,6 @@ extern "C" int cdn_codenet_dw_forward_range(const float *x, const float *s, cons
 // the fused inference schedule's protocol) -- no cdn_quantact_forward_partials update launch, no state-copy launch.
 // counters: cdn_quantact_arrive_words() zero-initialised 32-bit words per QuantAct (left zero by every call);
 // state_copy (8 words, may be NULL): the state after the update, for the backward pass.
-static cdn::QUpdate make_update(float *x_min, float *x_max, void *state, void *counters, int bits, double momentum) {
-  return cdn::QUpdate{x_min, x_max, static_cast<unsigned *>(state), static_cast<unsigned *>(counters),
-                      (float)(momentum - 1.0), (float)(1.0 - momentum), bits, 1};
-}
 #define CDN_REQUIRE_UPDATE()                                                                                          \
   CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");                             \
   CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits)
@@ -1524,7 +1520,7 @@ extern "C" int cdn_codenet_scale_forward_update(const float *x, const float *w_s
                                                 float *x_min, float *x_max, void *state, void *counters, int bits,
                                                 double momentum, void *state_copy, void *stream) {
   CDN_REQUIRE_UPDATE();
-  const cdn::QUpdate qu = make_update(x_min, x_max, state, counters, bits, momentum);
+  const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
   return scale_forward_impl(x, w_scale, b_scale, s, N, C, H, W, lo, hi, nullptr, stream, &qu,
                             static_cast<unsigned *>(state_copy));
 }
@@ -1541,7 +1537,7 @@ extern "C" int cdn_codenet_dw_forward_update(const float *x, const float *s, con
                                              void *state, void *counters, int bits, double momentum, void *state_copy,
                                              void *stream) {
   CDN_REQUIRE_UPDATE();
-  const cdn::QUpdate qu = make_update(x_min, x_max, state, counters, bits, momentum);
+  const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
   unsigned *copy = static_cast<unsigned *>(state_copy);
   // (up2: x, s are the STORED tensors, H x W the up-sampled resolution -- cdn_codenet_dw_up2_forward's convention)
   if (up2) return dw_up2_forward_impl(x, s, w_dw, d, N, C, H, W, nullptr, stream, &qu, copy);

@@ -809,7 +809,7 @@ namespace {
 // (L + zp) / scale with L the 8-bit code of the running QuantAct (quant_modules.py:203-225), the weight is q / ws with q
 // the 4-bit per-channel symmetric code (quant_utils.py:207-225).  pointwise_kernel multiplies the two fp32 disguises on
 // v_mfma_f32_32x32x2_f32 -- the fp32 VECTOR rate, 71 / 32 / 41 us at the step's three stages (4.3 GFLOP at 157 TFLOP/s
-// is 27 us at stage 0 before anything else) -- where the inference schedule (pwi8_kernel, codenet_fused.hip) sums the
+// is 27 us at stage 0 before anything else) -- where the inference schedule (pwi8_kernel, codenet_pointwise.hip) sums the
 // integers exactly:  y = (sum_k (L_k + zp) q_k) / (scale ws) + b, one rounding instead of K.  This is that kernel for
 // the training path's NCHW layout, where the MFMA operand layouts need no staging at all:
 //   A  (rows = output channels)  the weight codes from a k-blocked copy [window][column][32 B] made by
@@ -1120,7 +1120,7 @@ pwi8n_kernel(const float *__restrict__ D, const unsigned *__restrict__ dq, const
 // ------------------------------------------------------------------------------------------------------
 // pwb3n_kernel (round 5): the DATA GRADIENT of conv_channel in the QAT step,
 //   grad_d[n][c][p] = sum_co w_q[co][c] grad_y[n][co][p],   w_q = q / ws (4-bit codes),
-// on the bf16 matrix cores with EXACT products (pwb3_kernel's split, codenet_fused.hip): g' = grad_y / ws[co] is cut
+// on the bf16 matrix cores with EXACT products (pwb3_kernel's split, codenet_pointwise.hip): g' = grad_y / ws[co] is cut
 // into three bf16 terms by truncation (8 + 8 + 8 significant bits: hi + mid + lo == g' exactly), the codes are exact in
 // bf16, every product is exact in fp32 and the accumulation is fp32 -- 3 v_mfma_f32_32x32x16_bf16 per 16 k where
 // pointwise_kernel issues 8 v_mfma_f32_32x32x2_f32 (39 / 33 / 57 us at the step's three stages, matrix-core bound).
@@ -1266,7 +1266,7 @@ extern "C" int cdn_codenet_pointwise_i8_forward_range(const float *d, const void
                                                       const float *bias, float *y, int64_t N, int64_t C, int64_t Co,
                                                       int64_t HW, float *partials, void *workspace,
                                                       size_t workspace_bytes, void *stream) {
-  const cdn::QUpdate none{nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 8, 0};
+  const cdn::QUpdate none = cdn::no_qupdate();
   return pointwise_i8_forward_impl(d, d_state, w_q, bias, y, N, C, Co, HW, partials, workspace, workspace_bytes, stream,
                                    none, 0);
 }
@@ -1280,8 +1280,7 @@ extern "C" int cdn_codenet_pointwise_i8_forward_update(const float *d, const voi
                                                        void *counters, int bits, double momentum, void *stream) {
   CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");
   CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
-  const cdn::QUpdate qu{x_min, x_max, static_cast<unsigned *>(state), static_cast<unsigned *>(counters),
-                        (float)(momentum - 1.0), (float)(1.0 - momentum), bits, 1};
+  const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
   return pointwise_i8_forward_impl(d, d_state, w_q, bias, y, N, C, Co, HW, nullptr, workspace, workspace_bytes, stream,
                                    qu, relu_range);
 }

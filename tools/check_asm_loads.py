@@ -1,4 +1,4 @@
-"""ISA check for kernels whose global loads are inline asm behind explicit s_waitcnt (pwi8s_kernel, codenet_fused.hip).
+"""ISA check for kernels whose global loads are inline asm behind explicit s_waitcnt (pwi8s_kernel, codenet_pointwise.hip).
 
 The compiler does not know that the destination of an `asm volatile("global_load_dwordx4 %0, ...")` is written
 asynchronously: any copy, spill or use it places between the load and the s_waitcnt vmcnt(N) that covers it reads the

@@ -10,7 +10,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "codenet_amd", "csrc")
-# kernel name fragment -> (max VGPRs incl. AGPRs, or None) ; spills / scratch must be zero for all of them
+# codenet_fused.hip and codenet_pointwise.hip: kernel name fragment -> (max VGPRs incl. AGPRs, or None) ; spills / scratch
+# must be zero for all of them
 BUDGET = {
     "dw2_kernelILi64ELb0ELb0ELb1ELi1024": 128,    # stage 0, W4A8 (NCHW input, s quantised)
     "dw2_kernelILi64ELb0ELb0ELb0ELi1024": 128,    # stage 0, fp32
@@ -91,6 +92,7 @@ def kernel_resources(src="codenet_fused.hip", extra=()):
 
 def check():
     res = kernel_resources()
+    res.update(kernel_resources("codenet_pointwise.hip"))
     problems = []
     res_l = kernel_resources("codenet_layers.hip")
     for frag, cap in BUDGET_LAYERS.items():

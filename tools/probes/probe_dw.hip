@@ -1,6 +1,7 @@
 // Probe: phase timeline of the gather kernels from in-kernel stamps (thread 0 of each workgroup:
 // 0 start, 1 staging issued+stored, 2 barrier passed, 3 gather done (thread 0's wave), 4 finish done).
-// Includes the product source so the kernels are exactly the shipped ones.
+// Includes the product source so the kernels are exactly the shipped ones; everything else of the library (the
+// pointwise file with its stamp region among it) comes from libcodenet_dcn_stamps.so (`make stamps`) at link time.
 #define CDN_STAMPS 1
 #include "../../codenet_amd/csrc/codenet_fused.hip"
 #include "../../codenet_amd/csrc/cdn_common.hip"
@@ -10,7 +11,7 @@
 
 static void report(const char *name, int nwg, float us_kernel) {
   std::vector<unsigned long long> st(nwg * 8);
-  (void)hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(cdn_stamps), st.size() * 8);
+  (void)hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(cdn_stamps), st.size() * 8, 16384 * 8);      // region 1: the gather
   unsigned long long t0 = ~0ull, t1 = 0;
   for (int i = 0; i < nwg; ++i) { t0 = std::min(t0, st[i * 8]); t1 = std::max(t1, st[i * 8 + 4]); }
   double ph[4] = {0, 0, 0, 0};
@@ -69,19 +70,22 @@ int main() {
   cdn::QUpdate qu{xmin, xmax, state, counters, -0.01f, 0.01f, 8, 1};
   // stage 0: C=1024, 16x16, NCHW, up=0
   {
-    auto run = [&] { launch_dw2<64>(false, x, nullptr, s_raw, sstate, wd, d, qu, N, 1024, 16, 16, 0, nullptr); };
+    const GatherPlan gp = plan_gather(N, 1024, 16, 16, 0, false, 1 /* per-item kernels */, false, 0);
+    auto run = [&] { launch_dw2<64>(gp, false, x, nullptr, s_raw, sstate, wd, d, qu, 1024, 16, 16, 0, nullptr); };
     float us = time_us(run); run(); (void)hipDeviceSynchronize();
     report("stage0 dw2<64> 16x16", 16 * N, us);
   }
   // stage 1: C=256, 32x32 from 16x16 NHWC, up=1  -> dw2u<64>
   {
-    auto run = [&] { launch_dw2<64>(true, x, xstate, s_raw, sstate, wd, d, qu, N, 256, 32, 32, 1, nullptr); };
+    const GatherPlan gp = plan_gather(N, 256, 32, 32, 1, true, 0, true, 0);
+    auto run = [&] { launch_dw2<64>(gp, true, x, xstate, s_raw, sstate, wd, d, qu, 256, 32, 32, 1, nullptr); };
     float us = time_us(run); run(); (void)hipDeviceSynchronize();
     report("stage1 dw2u<64> 32x32", 4 * N, us);
   }
   // stage 2: C=128, 64x64 from 32x32 NHWC, up=1 -> dw2u<32>
   {
-    auto run = [&] { launch_dw2<32>(true, x, xstate, s_raw, sstate, wd, d, qu, N, 128, 64, 64, 1, nullptr); };
+    const GatherPlan gp = plan_gather(N, 128, 64, 64, 1, true, 0, true, 0);
+    auto run = [&] { launch_dw2<32>(gp, true, x, xstate, s_raw, sstate, wd, d, qu, 128, 64, 64, 1, nullptr); };
     float us = time_us(run); run(); (void)hipDeviceSynchronize();
     report("stage2 dw2u<32> 64x64", 4 * N, us);
   }
