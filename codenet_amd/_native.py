@@ -167,6 +167,14 @@ _SIGNATURES = {
     "cdn_codenet_head_dw_backward_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
     "cdn_codenet_head_dw_backward": (_i, [_vp, _vp, _i64] + [_vp] * 5 + [_i64, _vp, _vp] + [_i64] * 4
                                      + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_pointwise_forward_pitched": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i64] + [_i64] * 4 + [_i, _vp, _vp]),
+    "cdn_codenet_pointwise_wgrad_pitched": (_i, [_vp, _vp, _i64, _vp, _vp] + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_unit_dw_forward": (_i, [_vp, _i64] + [_vp] * 4 + [_i64] * 4 + [_i] + [_vp] * 4 + [_i, _d, _i, _vp, _vp]),
+    "cdn_codenet_unit_dw_backward_workspace_bytes": (ctypes.c_size_t, [_i64] * 4 + [_i]),
+    "cdn_codenet_unit_dw_backward": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _vp, _vp] + [_i64] * 4
+                                     + [_i, _vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_unit_join_forward": (_i, [_vp, _vp, _vp, _i, _vp] + [_i64] * 4 + [_vp]),
+    "cdn_codenet_unit_join_backward": (_i, [_vp, _vp, _vp, _i, _vp] + [_i64] * 4 + [_vp]),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

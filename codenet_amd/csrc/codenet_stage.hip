@@ -1097,7 +1097,9 @@ __global__ void __launch_bounds__(256)
 pointwise_kernel(const float *__restrict__ D, const float *__restrict__ Wp,
                  const float *__restrict__ bias, const float *__restrict__ ep_scale,
                  const float *__restrict__ ep_shift, float *__restrict__ Y, int C, int Co, int HW,
-                 int relu, float2 *__restrict__ mm, const unsigned *__restrict__ dq) {
+                 int relu, float2 *__restrict__ mm, const unsigned *__restrict__ dq, long d_pitch, long y_pitch) {
+  // d_pitch / y_pitch: elements between the images of D / Y (C * HW / Co * HW for whole tensors; larger where D or Y is a
+  // channel slice of a wider NCHW tensor, cdn_codenet_pointwise_forward_pitched)
   // K tiles of 32, the NEXT tile's global loads (4 x 16 B per thread) in flight behind the 16 MFMAs of the
   // current one: with one 16-deep tile and no prefetch every tile paid a full global-load latency (50 TF at
   // the stage-0 shape; the QAT step runs this kernel six times: forward and data gradient of three stages)
@@ -1107,7 +1109,7 @@ pointwise_kernel(const float *__restrict__ D, const float *__restrict__ Wp,
   const int m0 = blockIdx.y * kPwBM, p0 = blockIdx.x * kPwBN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-  const float *Dn = D + (long)n * C * HW;
+  const float *Dn = D + (long)n * d_pitch;
   f32x16 acc = {0};
   // staging: A tile 64(m) x 32(k): thread -> (m = tid>>2, 8 consecutive k from (tid&3)*8)
   //          B tile 32(k) x 64(n): thread -> (k = tid>>4 and +16, 4 pixels from (tid&15)*4)
@@ -1115,7 +1117,7 @@ pointwise_kernel(const float *__restrict__ D, const float *__restrict__ Wp,
   const int bk = tid >> 4, bn = (tid & 15) * 4;
   // 16-byte loads only when the rows are 16-byte aligned: the public entry point puts no alignment requirement on
   // w_pw / d (a weight view at a 4-byte offset takes the scalar path)
-  const bool hw4 = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(D) & 15) == 0;
+  const bool hw4 = (HW & 3) == 0 && (d_pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(D) & 15) == 0;
   const bool c4 = (C & 3) == 0 && (reinterpret_cast<uintptr_t>(Wp) & 15) == 0;
   float a[8], b[8];
   // dq != NULL (training path): D holds PRE-quantisation values and is fake-quantised with that QuantAct state while
@@ -1199,7 +1201,7 @@ pointwise_kernel(const float *__restrict__ D, const float *__restrict__ Wp,
       if (bias) v += bias[row];
       if (ep_scale) v = fmaf(v, ep_scale[row], ep_shift[row]);
       if (relu) v = cdn::relu_keep_nan(v);
-      Y[((long)n * Co + row) * HW + col] = v;
+      Y[(long)n * y_pitch + (long)row * HW + col] = v;
       mn = fminf(mn, v);
       mx = fmaxf(mx, v);
       has_nan |= (v != v);
@@ -1546,8 +1548,11 @@ extern "C" int cdn_codenet_dw_forward_update(const float *x, const float *s, con
 
 static int pointwise_forward_impl(const float *d, const float *w_pw, const float *bias, const float *ep_scale,
                                   const float *ep_shift, float *y, int64_t N, int64_t C, int64_t Co, int64_t HW,
-                                  int relu, float *partials, void *stream, const void *d_state = nullptr) {
+                                  int relu, float *partials, void *stream, const void *d_state = nullptr,
+                                  int64_t d_pitch = 0, int64_t y_pitch = 0) {
   CDN_REQUIRE(d && w_pw && y, CDN_ERR_ARG, "null tensor pointer");
+  if (d_pitch == 0) d_pitch = C * HW;      // (0: a whole tensor)
+  if (y_pitch == 0) y_pitch = Co * HW;
   CDN_REQUIRE((ep_scale == nullptr) == (ep_shift == nullptr), CDN_ERR_ARG,
               "ep_scale and ep_shift must both be set or both be NULL");
   CDN_REQUIRE(N > 0 && C > 0 && Co > 0 && HW > 0, CDN_ERR_ARG, "non-positive size");
@@ -1557,7 +1562,8 @@ static int pointwise_forward_impl(const float *d, const float *w_pw, const float
   pointwise_kernel<<<grid, 256, 0, cdn::as_stream(stream)>>>(d, w_pw, bias, ep_scale, ep_shift, y,
                                                              (int)C, (int)Co, (int)HW, relu,
                                                              reinterpret_cast<float2 *>(partials),
-                                                             static_cast<const unsigned *>(d_state));
+                                                             static_cast<const unsigned *>(d_state), (long)d_pitch,
+                                                             (long)y_pitch);
   return cdn::check_launch("codenet pointwise forward");
 }
 
@@ -1578,6 +1584,21 @@ extern "C" int cdn_codenet_pointwise_forward_range(const float *d, const void *d
                                                    float *partials, void *stream) {
   CDN_REQUIRE(partials || d_state, CDN_ERR_ARG, "neither partials nor d_state: use cdn_codenet_pointwise_forward");
   return pointwise_forward_impl(d, w_pw, bias, ep_scale, ep_shift, y, N, C, Co, HW, relu, partials, stream, d_state);
+}
+
+// The same kernel with d and / or y a channel slice of a wider NCHW tensor, addressed in place through an image pitch
+// (the QAT step of the ShuffleNetV2 units: x[:, h:] as input, grad_x[:, h:] as output).  d_state / partials may be NULL.
+extern "C" int cdn_codenet_pointwise_forward_pitched(const float *d, int64_t d_image_pitch, const void *d_state,
+                                                     const float *w_pw, const float *bias, float *y,
+                                                     int64_t y_image_pitch, int64_t N, int64_t C, int64_t Co, int64_t HW,
+                                                     int relu, float *partials, void *stream) {
+  CDN_REQUIRE(N > 0 && C > 0 && Co > 0 && HW > 0, CDN_ERR_ARG, "non-positive size");
+  CDN_REQUIRE(d_image_pitch >= C * HW, CDN_ERR_ARG, "image pitch of d below C * HW");
+  CDN_REQUIRE(y_image_pitch >= Co * HW, CDN_ERR_ARG, "image pitch of y below Co * HW");
+  CDN_REQUIRE(N * d_image_pitch < (1ll << 31) && N * y_image_pitch < (1ll << 31), CDN_ERR_UNSUPPORTED,
+              "shape too large");
+  return pointwise_forward_impl(d, w_pw, bias, nullptr, nullptr, y, N, C, Co, HW, relu, partials, stream, d_state,
+                                d_image_pitch, y_image_pitch);
 }
 
 extern "C" int cdn_codenet_dw_backward_supported(int64_t H, int64_t W) {

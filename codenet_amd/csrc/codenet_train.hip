@@ -30,7 +30,9 @@ constexpr int kWgBM = 64, kWgBN = 64, kWgBK = 64, kWgLd = kWgBK + 4;
 __global__ void __launch_bounds__(256)
 pw_wgrad_kernel(const float *__restrict__ gy, const float *__restrict__ d, float *__restrict__ partial,
                 float *__restrict__ partial_b, int C, int Co, int HW, int chunks_per_img, int nchunks,
-                int chunks_per_slice, const unsigned *__restrict__ dq) {
+                int chunks_per_slice, const unsigned *__restrict__ dq, long d_pitch) {
+  // d_pitch: elements between the images of d (C * HW for a whole tensor; larger where d is a channel slice of a wider
+  // NCHW tensor, cdn_codenet_pointwise_wgrad_pitched)
   __shared__ __attribute__((aligned(16))) float As[kWgBM][kWgLd];
   __shared__ __attribute__((aligned(16))) float Bs[kWgBN][kWgLd];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -38,7 +40,7 @@ pw_wgrad_kernel(const float *__restrict__ gy, const float *__restrict__ d, float
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const int ch_lo = z * chunks_per_slice, ch_hi = min(nchunks, ch_lo + chunks_per_slice);
   const int lrow = tid >> 4, lk = (tid & 15) * 4;      // staging: rows lrow + 16*i, floats lk .. lk+3
-  const bool hw4 = (HW & 3) == 0;
+  const bool hw4 = (HW & 3) == 0 && (d_pitch & 3) == 0;
   f32x16 acc = {0};
   float4 ra[4], rb[4];
   // bias gradient = row sums of grad_y: taken by the workgroups of channel tile 0 from the A tiles as they pass
@@ -56,7 +58,7 @@ pw_wgrad_kernel(const float *__restrict__ gy, const float *__restrict__ d, float
                     ((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
   auto load = [&](int ch) {
     const int n = ch / chunks_per_img, p0 = (ch - n * chunks_per_img) * kWgBK;
-    const float *ga = gy + (long)n * Co * HW, *gb = d + (long)n * C * HW;
+    const float *ga = gy + (long)n * Co * HW, *gb = d + (long)n * d_pitch;
     if (fast) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -433,7 +435,10 @@ extern "C" size_t cdn_codenet_pointwise_wgrad_workspace_bytes(int64_t N, int64_t
 
 static int pointwise_wgrad_impl(const float *grad_y, const float *d, const void *d_state, float *grad_w, float *grad_b,
                                 int64_t N, int64_t C, int64_t Co, int64_t HW, void *workspace, size_t workspace_bytes,
-                                void *stream, bool f32_only = false) {
+                                void *stream, bool f32_only = false, int64_t d_pitch = 0) {
+  // (a pitched d with HW % 4 != 0 is read with scalar loads only: a slice at any 4-byte offset)
+  const bool scalar_slice = d_pitch != 0 && (HW & 3) != 0;
+  if (d_pitch == 0) d_pitch = C * HW;      // (0: a whole tensor)
   CDN_REQUIRE(grad_y && d && grad_w && workspace, CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(N > 0 && C > 0 && Co > 0 && HW > 0, CDN_ERR_ARG, "non-positive size");
   CDN_REQUIRE(N * C * HW < (1ll << 31) && N * Co * HW < (1ll << 31) && C * Co < (1ll << 31),
@@ -441,7 +446,7 @@ static int pointwise_wgrad_impl(const float *grad_y, const float *d, const void 
   CDN_REQUIRE(workspace_bytes >= cdn_codenet_pointwise_wgrad_workspace_bytes(N, C, Co, HW) &&
                   (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
               CDN_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
-  CDN_REQUIRE((reinterpret_cast<uintptr_t>(grad_y) & 15) == 0 && (reinterpret_cast<uintptr_t>(d) & 15) == 0,
+  CDN_REQUIRE((reinterpret_cast<uintptr_t>(grad_y) & 15) == 0 && (scalar_slice || (reinterpret_cast<uintptr_t>(d) & 15) == 0),
               CDN_ERR_ARG, "grad_y / d must be 16-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
 #if !defined(CDN_NO_WGRAD_Q3)
@@ -475,7 +480,7 @@ static int pointwise_wgrad_impl(const float *grad_y, const float *d, const void 
   float *partial_b = grad_b ? partial + (size_t)p.nz * Co * C : nullptr;
   pw_wgrad_kernel<<<dim3((unsigned)p.tiles_c, (unsigned)p.tiles_m, (unsigned)p.nz), 256, 0, st>>>(
       grad_y, d, partial, partial_b, (int)C, (int)Co, (int)HW, p.chunks_per_img, p.nchunks, p.per_slice,
-      static_cast<const unsigned *>(d_state));
+      static_cast<const unsigned *>(d_state), (long)d_pitch);
   int rc = cdn::check_launch("codenet pointwise weight gradient");
   if (rc) return rc;
   const long n = (long)(Co * C);
@@ -501,6 +506,18 @@ extern "C" int cdn_codenet_pointwise_wgrad_q_f32(const float *grad_y, const floa
                                                  void *workspace, size_t workspace_bytes, void *stream) {
   CDN_REQUIRE(d_state, CDN_ERR_ARG, "null pointer");
   return pointwise_wgrad_impl(grad_y, d, d_state, grad_w, grad_b, N, C, Co, HW, workspace, workspace_bytes, stream, true);
+}
+
+// cdn_codenet_pointwise_wgrad with d a channel slice of a wider NCHW tensor, read in place through an image pitch (the
+// QAT step of the ShuffleNetV2 units: x[:, h:]); always the f32-MFMA kernel, the same workspace
+extern "C" int cdn_codenet_pointwise_wgrad_pitched(const float *grad_y, const float *d, int64_t d_image_pitch,
+                                                   float *grad_w, float *grad_b, int64_t N, int64_t C, int64_t Co,
+                                                   int64_t HW, void *workspace, size_t workspace_bytes, void *stream) {
+  CDN_REQUIRE(N > 0 && C > 0 && Co > 0 && HW > 0, CDN_ERR_ARG, "non-positive size");
+  CDN_REQUIRE(d_image_pitch >= C * HW, CDN_ERR_ARG, "image pitch of d below C * HW");
+  CDN_REQUIRE(N * d_image_pitch < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
+  return pointwise_wgrad_impl(grad_y, d, nullptr, grad_w, grad_b, N, C, Co, HW, workspace, workspace_bytes, stream, true,
+                              d_image_pitch);
 }
 
 static int scale_backward_impl(const float *x, const float *grad_s, const float *s_clamped, float lo, float hi,

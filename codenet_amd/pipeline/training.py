@@ -1,4 +1,5 @@
-"""GraphedTrainStep: the QAT step of the deform-stage stack -- or of the detection tail, stages + heads -- as one HIP graph.
+"""GraphedTrainStep: the QAT step of the deform-stage stack -- or of the detection tail, stages + heads, or of the trunk,
+layers 1-4 in front of that tail -- as one HIP graph.
 
 Part of codenet_amd.pipeline (split by concern in round 6; `from codenet_amd import pipeline` exposes every name as
 before)."""
@@ -28,6 +29,32 @@ class DetectionTail(nn.Module):
         from ..functions.codenet_heads import forward_heads
         from ..functions.codenet_stage import forward_stage_blocks
         return [forward_heads(self.head_modules(), forward_stage_blocks(self.deconv_layers, feat))]
+
+
+class DetectionTrunk(nn.Module):
+    """Everything of the CoDeNet behind the stem as one module: layers 1-4 of the backbone, the deform stages and the
+    detection heads of `model` (modules SHARED, not copied).  forward(feat0) -> [{head: tensor}] from layer0's output.
+    After quantisation every kernel of its training step is this library's (functions/codenet_units.forward_units /
+    forward_layer4 in front of DetectionTail's chain); the stem keeps the module path and stays outside."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.heads = dict(model.heads)
+        for name in ("layer1", "layer2", "layer3", "layer4", "deconv_layers") + tuple(self.heads):
+            setattr(self, name, getattr(model, name))
+
+    def head_modules(self):
+        return {h: getattr(self, h) for h in self.heads}
+
+    def forward(self, feat0):
+        from ..functions.codenet_heads import forward_heads
+        from ..functions.codenet_stage import forward_stage_blocks
+        from ..functions.codenet_units import forward_layer4, forward_units
+        x = feat0
+        for layer in (self.layer1, self.layer2, self.layer3):
+            x = forward_units(layer, x)
+        x = forward_stage_blocks(self.deconv_layers, forward_layer4(self.layer4, x))
+        return [forward_heads(self.head_modules(), x)]
 
 
 def _stage_blocks_ok(seq):
@@ -66,13 +93,16 @@ class GraphedTrainStep:
     SCOPE.  Validated -- and accepted without `unvalidated=True` -- are (1) the stack of deform stages
     (``pipeline.build_hot_path`` / a quantised ``deconv_layers``, `is_stage_stack`) and (2) the detection tail,
     ``pipeline.DetectionTail(model)`` of a quantised model whose heads run on functions/codenet_heads.py
-    (`is_native_tail`): every kernel of those steps is this library's, every sum has one order.
+    (`is_native_tail`), and (3) the trunk, ``pipeline.DetectionTrunk(model)`` -- layers 1-4 of the backbone in front of
+    that tail, from layer0's output -- of a quantised model whose units run on functions/codenet_units.py
+    (`is_native_trunk`): every kernel of those steps is this library's, every sum has one order.
     tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
     bit-identical from a restored state whatever else the process does in between (a second model built before the capture
     taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
-    tests/test_gpu_heads_train.py shows replays of (2) with the native criterion bit-identical to the eager steps.
-    A network that also runs PyTorch-ROCm operators under autograd (the whole CoDeNet with its backbone, fp32 or
-    percentile heads, NATIVE_HEADS off) needs `unvalidated=True`; what was measured for it (tools/experiments/gts_probe*.py):
+    tests/test_gpu_heads_train.py shows replays of (2) with the native criterion bit-identical to the eager steps,
+    tests/test_gpu_units_train.py those of (3).
+    A network that also runs PyTorch-ROCm operators under autograd (the whole CoDeNet with its stem layer0, fp32 or
+    percentile heads or units, NATIVE_HEADS / NATIVE_UNITS off) needs `unvalidated=True`; what was measured for it (tools/experiments/gts_probe*.py):
       * parameters and gradients of a replay agree with any other replay FROM THE SAME STATE to ~1e-6 of their magnitude --
         with or without other work in between.  That residue is the framework's own backward (atomics), present in two
         eager runs too; after a quantiser amplifies it the loss trajectories of two runs part ways in the fifth digit by
@@ -86,10 +116,12 @@ class GraphedTrainStep:
         (``codenet_amd.losses.CtdetLoss``: its sums are fixed-order slabs of this library's own kernels)."""
 
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
-        if not unvalidated and not self.is_stage_stack(net) and not self.is_native_tail(net):
+        if not unvalidated and not self.is_stage_stack(net) and not self.is_native_tail(net) \
+                and not self.is_native_trunk(net):
             raise NotImplementedError(
-                "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages and for a "
-                "pipeline.DetectionTail whose heads run natively only; `net` "
+                "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for a "
+                "pipeline.DetectionTail whose heads run natively and for a pipeline.DetectionTrunk whose units run "
+                "natively only; `net` "
                 "holds other modules, whose PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass "
                 "unvalidated=True to capture it anyway (see the class docstring for what was measured).")
         self.static = [t.detach().clone() for t in example_inputs]
@@ -132,6 +164,17 @@ class GraphedTrainStep:
         from ..functions.codenet_heads import native_reason
         return (isinstance(net, DetectionTail) and _stage_blocks_ok(net.deconv_layers)
                 and native_reason(net.head_modules(), None) is None)
+
+    @staticmethod
+    def is_native_trunk(net):
+        """True for a pipeline.DetectionTrunk whose stages and heads are what `is_native_tail` accepts and whose layers 1-3
+        and layer4 functions/codenet_units runs natively (native_reason(layer, None) is None: QuantBaseNode units with the
+        default QuantAct settings, no hooks, NATIVE_UNITS on)."""
+        from ..functions.codenet_heads import native_reason as heads_reason
+        from ..functions.codenet_units import native_reason as units_reason
+        return (isinstance(net, DetectionTrunk) and _stage_blocks_ok(net.deconv_layers)
+                and heads_reason(net.head_modules(), None) is None
+                and all(units_reason(getattr(net, name), None) is None for name in ("layer1", "layer2", "layer3", "layer4")))
 
     def set_lr(self, value, group=None):
         """Write a new learning rate where the captured step reads it: the param group's lr must be a device TENSOR

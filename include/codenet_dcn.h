@@ -1095,6 +1095,65 @@ int cdn_codenet_head_dw_backward(const float *g, const float *w3, int64_t Co, co
                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The quantised ShuffleNetV2 units in the QAT step (QuantBaseNode, quant_modules.py:809-907; layers 1-3), per unit:
+ *   stride 1:  x1 = x[:, :h] (unchanged)                      x2 = x[:, h:]
+ *   stride 2:  x1 = act(relu(pw5(act4(dw4_s2(x)))))           x2 = x
+ *   both:      x2' = act(relu(pw3(act2(dw2_s(act1(relu(pw1(x2))))))))     out[:, 2j] = x1[:, j],  out[:, 2j+1] = x2'[:, j]
+ * NCHW fp32.  `act` is the ONE QuantAct a layer's units share.  The dense 1x1 convolutions and their gradients are the
+ * pointwise entries (the *_pitched ones where an operand is a channel slice); these are the pieces in between.  Every
+ * call takes a stream, allocates nothing, launches no memset node and is capturable; every floating-point sum has one
+ * order (no float atomics).  An "image pitch" is the distance in elements between two images of a tensor: a channel slice
+ * x[:, a:b] of [N][Cx][H][W] is (x + a * H * W, pitch Cx * H * W) and is read / written in place.
+ *
+ * cdn_codenet_pointwise_forward_pitched (replaces :602-604 / :599-600 on a slice, and the data gradient of pw1):
+ *   cdn_codenet_pointwise_forward_range (no affine epilogue) with image pitches for d and y; d_state and partials may be
+ *   NULL; partials holds cdn_codenet_pointwise_range_partials(N, Co, HW) pairs.  f32 MFMA, the bits of the unpitched call.
+ * cdn_codenet_pointwise_wgrad_pitched: cdn_codenet_pointwise_wgrad with an image pitch for d; the same workspace.
+ * cdn_codenet_unit_dw_forward (replaces quant_convbn2 / quant_convbn4 + the QuantAct behind them, :599, :603):
+ *   out [N][C][Ho][Wo] = dw3x3(a, w [C][9], stride 1 or 2, zero padding 1) + b (may be NULL), Ho = (H - 1) / stride + 1,
+ *   the RAW output (no ReLU), stored BEFORE quantisation.  in_state != NULL: a = fq(relu(in)) formed while loading with
+ *   that 8-word QuantAct state (snapshot); NULL: in holds final values, read as they are.  running != 0: the launch's last
+ *   workgroup updates the QuantAct behind out (x_min, x_max, state, counters = cdn_quantact_arrive_words() zero words,
+ *   left zero) from the signed extremes of out and writes state_copy (may be NULL); running == 0: not read.
+ *   Sum order of an output: taps in row-major order by fma from zero, then + b.
+ * cdn_codenet_unit_dw_backward: g [N][C][Ho][Wo] is the gradient of that raw output (straight-through QuantAct).
+ *   grad_in[Y][X] = sum of w[dy][dx] g[yo][xo] over the taps with Y + 1 - dy = stride * yo, X + 1 - dx = stride * xo
+ *   (row-major tap order by fma from zero; a gather), masked by in > 0 when in_state != NULL; written at
+ *   grad_in + n * grad_in_image_pitch + c * H * W, accumulate != 0: ADDED to what is stored there (by the one thread that
+ *   owns the pixel).  grad_in may be NULL.  grad_w [C][9], grad_b [C] (either may be NULL): OVERWRITTEN; per-workgroup
+ *   partials in `workspace` (cdn_codenet_unit_dw_backward_workspace_bytes, 16-byte aligned, every word written before it
+ *   is read) summed in index order by a second launch.
+ *   cdn_codenet_unit_dw_backward_workspace_bytes = round_up_256(C * chunks * 10 * 4), chunks = ceil(items / 256),
+ *   items = N * ceil(Ho / rows) * ceil(Wo / 4), rows = 8 where Ho >= 32 else 4.
+ * cdn_codenet_unit_join_forward (replaces the shared QuantAct's fake-quantisation + cat + channel_shuffle, :600 / :604-605):
+ *   out [N][2h][HW]: out[:, 2j + slot] = fq(relu(y3 [N][h][HW])) with act_state (the shared QuantAct's state AFTER the
+ *   update for this branch); x1 != NULL (slot 1 only): out[:, 2j] = x1[:, j] read at x1 + n * x1_image_pitch + j * HW.
+ * cdn_codenet_unit_join_backward: grad_y3 = grad_out[:, 2j + slot] where y3 > 0; grad_x1 != NULL (slot 1 only):
+ *   grad_x1 + n * pitch + j * HW = grad_out[:, 2j].
+ * 16-byte accesses where the widths are multiples of 4 and pointers / pitches 16-byte aligned, scalar ones otherwise.
+ * Sizes below 2^31 elements per tensor (CDN_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_codenet_pointwise_forward_pitched(const float *d, int64_t d_image_pitch, const void *d_state, const float *w_pw,
+                                          const float *bias, float *y, int64_t y_image_pitch, int64_t N, int64_t C,
+                                          int64_t Co, int64_t HW, int relu, float *partials, void *stream);
+int cdn_codenet_pointwise_wgrad_pitched(const float *grad_y, const float *d, int64_t d_image_pitch, float *grad_w,
+                                        float *grad_b, int64_t N, int64_t C, int64_t Co, int64_t HW, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+int cdn_codenet_unit_dw_forward(const float *in, int64_t in_image_pitch, const void *in_state, const float *w,
+                                const float *b, float *out, int64_t N, int64_t C, int64_t H, int64_t W, int stride,
+                                float *x_min, float *x_max, void *state, void *counters, int bits, double momentum,
+                                int running, void *state_copy, void *stream);
+size_t cdn_codenet_unit_dw_backward_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int stride);
+int cdn_codenet_unit_dw_backward(const float *g, const float *in, int64_t in_image_pitch, const void *in_state,
+                                 const float *w, float *grad_in, int64_t grad_in_image_pitch, int accumulate,
+                                 float *grad_w, float *grad_b, int64_t N, int64_t C, int64_t H, int64_t W, int stride,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int cdn_codenet_unit_join_forward(const float *y3, const void *act_state, float *out, int slot, const float *x1,
+                                  int64_t x1_image_pitch, int64_t N, int64_t h, int64_t HW, void *stream);
+int cdn_codenet_unit_join_backward(const float *grad_out, const float *y3, float *grad_y3, int slot, float *grad_x1,
+                                   int64_t grad_x1_image_pitch, int64_t N, int64_t h, int64_t HW, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

@@ -73,6 +73,13 @@ BUDGET_PREPROC = {"pre_process_kernel": 64, "crop_sum_kernel": 64, "color_aug_ke
 BUDGET_HEADS_TRAIN = {"head_dw_fwd_kernel": 64, "head_tail_fwd_kernel": 64, "head_dw_bwd_kernelILi": 128,
                       "head_dw_bwd_reduce_kernel": 64}
 
+# codenet_units_train.hip (built without the SLP vectoriser, as codenet_heads_train.hip): the same kind of bandwidth-bound
+# register-window kernels -- the depthwise forward (3 x 6 / 3 x 9 window) and the joins at eight waves per SIMD (64 VGPRs;
+# 33-52 / 16-22 when written), the depthwise backward with its input and gradient windows and ten sums at four (128;
+# 64-96), no scratch
+BUDGET_UNITS_TRAIN = {"unit_dw_fwd_kernel": 64, "unit_join_fwd_kernel": 64, "unit_join_bwd_kernel": 64,
+                      "unit_dw_bwd_kernelILi": 128, "unit_dw_bwd_reduce_kernel": 64}
+
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
     with tempfile.TemporaryDirectory() as tmp:
@@ -109,7 +116,8 @@ def check():
     for src, extra, budget in (("codenet_stage.hip", ("-fno-slp-vectorize",), BUDGET_STAGE), ("dcn_generic.hip", (), BUDGET_GENERIC),
                                ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE),
                                ("codenet_loss.hip", (), BUDGET_LOSS), ("codenet_preproc.hip", (), BUDGET_PREPROC),
-                               ("codenet_heads_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_TRAIN)):
+                               ("codenet_heads_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_TRAIN),
+                               ("codenet_units_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_TRAIN)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -136,7 +144,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))
