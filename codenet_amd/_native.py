@@ -175,6 +175,11 @@ _SIGNATURES = {
                                      + [_i, _vp, ctypes.c_size_t, _vp]),
     "cdn_codenet_unit_join_forward": (_i, [_vp, _vp, _vp, _i, _vp] + [_i64] * 4 + [_vp]),
     "cdn_codenet_unit_join_backward": (_i, [_vp, _vp, _vp, _i, _vp] + [_i64] * 4 + [_vp]),
+    "cdn_codenet_stem_train_forward": (_i, [_vp] * 4 + [_i64] * 4 + [_i] + [_vp] * 4 + [_i, _d, _i, _vp, _vp]),
+    "cdn_codenet_stem_pool_forward": (_i, [_vp] * 3 + [_i64] * 4 + [_vp]),
+    "cdn_codenet_stem_pool_backward": (_i, [_vp] * 4 + [_i64] * 4 + [_vp]),
+    "cdn_codenet_stem_backward_workspace_bytes": (ctypes.c_size_t, [_i64] * 3 + [_i]),
+    "cdn_codenet_stem_backward": (_i, [_vp] * 5 + [_i64] * 4 + [_i, _vp, ctypes.c_size_t, _vp]),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

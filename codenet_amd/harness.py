@@ -224,10 +224,11 @@ class PoseShuffleNetV2(nn.Module):
                 return [self._fheads(*stages.forward_nhwc(feat, fq, hw))]
             x = self.layer4(self.layer3(self.layer2(self.layer1(self.layer0(x)))))
             return [self._fheads(*self._fpath.forward_nhwc(x))]
-        # == self.layer4(self.layer3(self.layer2(self.layer1(self.layer0(x))))); the quantised units and layer4 of a QAT
-        # step as native autograd functions (functions/codenet_units.py), layer0 module by module
+        # == self.layer4(self.layer3(self.layer2(self.layer1(self.layer0(x))))); the quantised stem, units and layer4 of a
+        # QAT step as native autograd functions (functions/codenet_stem.py, functions/codenet_units.py)
+        from .functions.codenet_stem import forward_stem
         from .functions.codenet_units import forward_layer4, forward_units
-        x = self.layer0(x)
+        x = forward_stem(self.layer0, x)
         for layer in (self.layer1, self.layer2, self.layer3):
             x = forward_units(layer, x)
         x = forward_layer4(self.layer4, x)

@@ -18,5 +18,5 @@ from .hotpath import (FusedHotPath)      # noqa: F401
 from .heads import (FusedHeads)      # noqa: F401
 from .backbone import (FusedBackbone)      # noqa: F401
 from .serving import (cover_frozen_ranges, _widen, calibrate_serving, prepare_serving, FrozenHotPath, FrozenBackbone)      # noqa: F401
-from .training import (GraphedTrainStep, DetectionTail, DetectionTrunk)      # noqa: F401
+from .training import (GraphedTrainStep, DetectionNet, DetectionTail, DetectionTrunk)      # noqa: F401
 from . import backbone, common, distributed, heads, hotpath, serving, training      # noqa: F401

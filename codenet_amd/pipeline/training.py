@@ -1,5 +1,5 @@
 """GraphedTrainStep: the QAT step of the deform-stage stack -- or of the detection tail, stages + heads, or of the trunk,
-layers 1-4 in front of that tail -- as one HIP graph.
+layers 1-4 in front of that tail, or of the whole network from the image -- as one HIP graph.
 
 Part of codenet_amd.pipeline (split by concern in round 6; `from codenet_amd import pipeline` exposes every name as
 before)."""
@@ -35,7 +35,7 @@ class DetectionTrunk(nn.Module):
     """Everything of the CoDeNet behind the stem as one module: layers 1-4 of the backbone, the deform stages and the
     detection heads of `model` (modules SHARED, not copied).  forward(feat0) -> [{head: tensor}] from layer0's output.
     After quantisation every kernel of its training step is this library's (functions/codenet_units.forward_units /
-    forward_layer4 in front of DetectionTail's chain); the stem keeps the module path and stays outside."""
+    forward_layer4 in front of DetectionTail's chain); the stem stays outside (DetectionNet takes it in)."""
 
     def __init__(self, model):
         super().__init__()
@@ -51,6 +51,34 @@ class DetectionTrunk(nn.Module):
         from ..functions.codenet_stage import forward_stage_blocks
         from ..functions.codenet_units import forward_layer4, forward_units
         x = feat0
+        for layer in (self.layer1, self.layer2, self.layer3):
+            x = forward_units(layer, x)
+        x = forward_stage_blocks(self.deconv_layers, forward_layer4(self.layer4, x))
+        return [forward_heads(self.head_modules(), x)]
+
+
+class DetectionNet(nn.Module):
+    """The whole CoDeNet as one module for the QAT step: the stem, layers 1-4 of the backbone, the deform stages and the
+    detection heads of `model` (modules SHARED, not copied).  forward(img) -> [{head: tensor}] from the image, always through
+    the training chain functions/codenet_stem.forward_stem -> codenet_units.forward_units x 3 -> forward_layer4 ->
+    codenet_stage.forward_stage_blocks -> codenet_heads.forward_heads -- never through the inference schedules the model's
+    own forward dispatches on.  After quantisation every kernel of its training step is this library's."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.heads = dict(model.heads)
+        for name in ("layer0", "layer1", "layer2", "layer3", "layer4", "deconv_layers") + tuple(self.heads):
+            setattr(self, name, getattr(model, name))
+
+    def head_modules(self):
+        return {h: getattr(self, h) for h in self.heads}
+
+    def forward(self, img):
+        from ..functions.codenet_heads import forward_heads
+        from ..functions.codenet_stage import forward_stage_blocks
+        from ..functions.codenet_stem import forward_stem
+        from ..functions.codenet_units import forward_layer4, forward_units
+        x = forward_stem(self.layer0, img)
         for layer in (self.layer1, self.layer2, self.layer3):
             x = forward_units(layer, x)
         x = forward_stage_blocks(self.deconv_layers, forward_layer4(self.layer4, x))
@@ -95,14 +123,17 @@ class GraphedTrainStep:
     ``pipeline.DetectionTail(model)`` of a quantised model whose heads run on functions/codenet_heads.py
     (`is_native_tail`), and (3) the trunk, ``pipeline.DetectionTrunk(model)`` -- layers 1-4 of the backbone in front of
     that tail, from layer0's output -- of a quantised model whose units run on functions/codenet_units.py
-    (`is_native_trunk`): every kernel of those steps is this library's, every sum has one order.
+    (`is_native_trunk`), and (4) the whole network, ``pipeline.DetectionNet(model)`` -- the stem in front of that trunk,
+    from the image -- of a quantised model whose stem runs on functions/codenet_stem.py (`is_native_net`): every kernel of
+    those steps is this library's, every sum has one order.
     tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
     bit-identical from a restored state whatever else the process does in between (a second model built before the capture
     taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
     tests/test_gpu_heads_train.py shows replays of (2) with the native criterion bit-identical to the eager steps,
-    tests/test_gpu_units_train.py those of (3).
-    A network that also runs PyTorch-ROCm operators under autograd (the whole CoDeNet with its stem layer0, fp32 or
-    percentile heads or units, NATIVE_HEADS / NATIVE_UNITS off) needs `unvalidated=True`; what was measured for it (tools/experiments/gts_probe*.py):
+    tests/test_gpu_units_train.py those of (3), tests/test_gpu_stem_train.py those of (4).
+    A network that also runs PyTorch-ROCm operators under autograd (a bare harness.PoseShuffleNetV2, whose forward
+    dispatches on inference schedules the capture was never validated for -- wrap it in DetectionNet --, an fp32 or
+    percentile stem, heads or units, NATIVE_STEM / NATIVE_HEADS / NATIVE_UNITS off) needs `unvalidated=True`; what was measured for it (tools/experiments/gts_probe*.py):
       * parameters and gradients of a replay agree with any other replay FROM THE SAME STATE to ~1e-6 of their magnitude --
         with or without other work in between.  That residue is the framework's own backward (atomics), present in two
         eager runs too; after a quantiser amplifies it the loss trajectories of two runs part ways in the fifth digit by
@@ -117,11 +148,11 @@ class GraphedTrainStep:
 
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
         if not unvalidated and not self.is_stage_stack(net) and not self.is_native_tail(net) \
-                and not self.is_native_trunk(net):
+                and not self.is_native_trunk(net) and not self.is_native_net(net):
             raise NotImplementedError(
                 "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for a "
-                "pipeline.DetectionTail whose heads run natively and for a pipeline.DetectionTrunk whose units run "
-                "natively only; `net` "
+                "pipeline.DetectionTail whose heads run natively, for a pipeline.DetectionTrunk whose units run "
+                "natively and for a pipeline.DetectionNet whose stem runs natively only; `net` "
                 "holds other modules, whose PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass "
                 "unvalidated=True to capture it anyway (see the class docstring for what was measured).")
         self.static = [t.detach().clone() for t in example_inputs]
@@ -174,6 +205,19 @@ class GraphedTrainStep:
         from ..functions.codenet_units import native_reason as units_reason
         return (isinstance(net, DetectionTrunk) and _stage_blocks_ok(net.deconv_layers)
                 and heads_reason(net.head_modules(), None) is None
+                and all(units_reason(getattr(net, name), None) is None for name in ("layer1", "layer2", "layer3", "layer4")))
+
+    @staticmethod
+    def is_native_net(net):
+        """True for a pipeline.DetectionNet whose layers 1-4, stages and heads are what `is_native_trunk` accepts and whose
+        stem functions/codenet_stem runs natively (native_reason(layer0, None) is None: the quantised 3 -> 24 stem with the
+        default QuantAct settings, no hooks, NATIVE_STEM on) -- image -> loss -> optimizer is then one chain of this
+        library's kernels."""
+        from ..functions.codenet_heads import native_reason as heads_reason
+        from ..functions.codenet_stem import native_reason as stem_reason
+        from ..functions.codenet_units import native_reason as units_reason
+        return (isinstance(net, DetectionNet) and _stage_blocks_ok(net.deconv_layers)
+                and heads_reason(net.head_modules(), None) is None and stem_reason(net.layer0, None) is None
                 and all(units_reason(getattr(net, name), None) is None for name in ("layer1", "layer2", "layer3", "layer4")))
 
     def set_lr(self, value, group=None):

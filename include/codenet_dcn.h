@@ -1154,6 +1154,44 @@ int cdn_codenet_unit_join_backward(const float *grad_out, const float *y3, float
                                    int64_t grad_x1_image_pitch, int64_t N, int64_t h, int64_t HW, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The quantised stem in the QAT step (layer0 after quantisation: QuantBnConv2d(8) 3 -> 24, 3x3, stride 4 or 2, padding 1,
+ * then ReLU -> QuantAct [-> MaxPool2d(3, 2, 1)]).  NCHW fp32; the weights come folded and fake-quantised from
+ * cdn_codenet_weight_prep_ranked.  Every call takes a stream, allocates nothing, launches no memset node and is capturable;
+ * every floating-point sum has one order (no float atomics).  The image takes no gradient.
+ *
+ * cdn_codenet_stem_train_forward: y0 [N][24][Ho][Wo] = conv3x3(img [N][3][H][W], w [24][27], stride, zero padding 1) + b
+ *   (may be NULL), Ho = (H - 1) / stride + 1, the RAW output, stored BEFORE ReLU and quantisation.  Co must be 24, stride 2
+ *   or 4.  running != 0: the launch's last workgroup updates the QuantAct behind the stem (x_min, x_max, state, counters =
+ *   cdn_quantact_arrive_words() zero words, left zero) from the extremes of max(y0, 0) and writes state_copy (may be NULL);
+ *   running == 0: not read.  Sum order of an output: the 27 taps in (ci, dy, dx) order by fma from zero, then + b.
+ *   The un-pooled stem's output is cdn_quantact_relu_apply(y0, ..., state_copy).
+ * cdn_codenet_stem_pool_forward: out [N][C][Hp][Wp] = fq(relu(max over the 3x3 window, stride 2, padding 1, of
+ *   y0 [N][C][H][W])) with act_state, Hp = (H - 1) / 2 + 1: the pool of the quantised values (both maps are monotone).
+ * cdn_codenet_stem_pool_backward: grad_y0 [N][C][H][W] from g [N][C][Hp][Wp]: a window's gradient goes to its first maximum
+ *   in row-major scan order (val > max || isnan(val)), compared on fq(relu(y0)) with act_state; a pixel adds the windows it
+ *   won in row-major window order (a gather, every element written exactly once), masked by y0 > 0.
+ * cdn_codenet_stem_backward: grad_b [24] = sum g', grad_w [24][27] = sum g'[n][c][oy][ox] img[n][ci][oy S + dy - 1][ox S +
+ *   dx - 1] (zero outside the image), g' = g where y0 > 0 else 0 when y0 != NULL, g' = g when y0 == NULL (g already masked:
+ *   the pool backward's output).  Either result may be NULL; both are OVERWRITTEN.  Per-workgroup partials in `workspace`
+ *   (16-byte aligned, every word written before it is read) summed in chunk order by a second launch.
+ *   cdn_codenet_stem_backward_workspace_bytes = round_up_256(6 * chunks * 112 * 4), chunks = ceil(P / (256 * T)),
+ *   P = N * Ho * Wo, T = min(8, max(1, P / 1024)); 0 for arguments the call refuses.
+ * Sizes below 2^31 elements per tensor (CDN_ERR_UNSUPPORTED beyond); a workspace that is too small is CDN_ERR_WORKSPACE.
+ * Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_codenet_stem_train_forward(const float *img, const float *w, const float *b, float *y0, int64_t N, int64_t H,
+                                   int64_t W, int64_t Co, int stride, float *x_min, float *x_max, void *state,
+                                   void *counters, int bits, double momentum, int running, void *state_copy, void *stream);
+int cdn_codenet_stem_pool_forward(const float *y0, const void *act_state, float *out, int64_t N, int64_t C, int64_t H,
+                                  int64_t W, void *stream);
+int cdn_codenet_stem_pool_backward(const float *g, const float *y0, const void *act_state, float *grad_y0, int64_t N,
+                                   int64_t C, int64_t H, int64_t W, void *stream);
+size_t cdn_codenet_stem_backward_workspace_bytes(int64_t N, int64_t H, int64_t W, int stride);
+int cdn_codenet_stem_backward(const float *g, const float *y0, const float *img, float *grad_w, float *grad_b, int64_t N,
+                              int64_t H, int64_t W, int64_t Co, int stride, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

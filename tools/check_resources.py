@@ -80,6 +80,12 @@ BUDGET_HEADS_TRAIN = {"head_dw_fwd_kernel": 64, "head_tail_fwd_kernel": 64, "hea
 BUDGET_UNITS_TRAIN = {"unit_dw_fwd_kernel": 64, "unit_join_fwd_kernel": 64, "unit_join_bwd_kernel": 64,
                       "unit_dw_bwd_kernelILi": 128, "unit_dw_bwd_reduce_kernel": 64}
 
+# codenet_stem_train.hip (built without the SLP vectoriser, as codenet_units_train.hip): the forward (27 inputs, one
+# accumulator at a time) and the pool kernels (a 5 x 5 patch) at eight waves per SIMD (64 VGPRs; 57 / 14 / 50 when written);
+# the weight gradient holds 4 x 28 sums beside the 27-value patch and runs at three (168; 160), no scratch
+BUDGET_STEM_TRAIN = {"stem_train_fwd_kernel": 64, "stem_pool_fwd_kernel": 64, "stem_pool_bwd_kernel": 64,
+                     "stem_wgrad_kernel": 168, "stem_wgrad_reduce_kernel": 64}
+
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
     with tempfile.TemporaryDirectory() as tmp:
@@ -117,7 +123,8 @@ def check():
                                ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE),
                                ("codenet_loss.hip", (), BUDGET_LOSS), ("codenet_preproc.hip", (), BUDGET_PREPROC),
                                ("codenet_heads_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_TRAIN),
-                               ("codenet_units_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_TRAIN)):
+                               ("codenet_units_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_TRAIN),
+                               ("codenet_stem_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_TRAIN)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -144,7 +151,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))
