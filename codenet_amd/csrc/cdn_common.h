@@ -540,3 +540,27 @@ int clear_pointwise_stamps();
   do {                               \
     if (!(cond)) return cdn::fail(code, __VA_ARGS__); \
   } while (0)
+
+namespace cdn {
+// ---- what the entry points check alike ----------------------------------------------------------
+inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// a caller's workspace against the size its *_workspace_bytes function answers
+inline int check_workspace(const void *workspace, size_t bytes, size_t need) {
+  CDN_REQUIRE(bytes >= need && aligned16(workspace), CDN_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
+  return CDN_OK;
+}
+#ifdef __HIPCC__
+// The QuantAct a producer launch updates in its last workgroup (block_minmax_finish), from the arguments of an entry
+// point; running == 0: nothing is measured (no_qupdate).
+inline int tracked_qupdate(QUpdate *qu, float *x_min, float *x_max, void *state, void *counters, int bits, double momentum,
+                           int running = 1) {
+  *qu = no_qupdate();
+  if (!running) return CDN_OK;
+  CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");
+  CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
+  *qu = make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
+  return CDN_OK;
+}
+#endif
+}  // namespace cdn

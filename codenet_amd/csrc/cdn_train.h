@@ -1,0 +1,127 @@
+// cdn_train.h -- what the kernels of the QAT step share (codenet_heads_train.hip, codenet_units_train.hip,
+// codenet_stem_train.hip): the fake-quantiser of a state snapshot, the register-window row loaders
+// of the depthwise kernels and the one protocol of the per-channel weight / bias gradient sums.
+//
+// The sums.  A workgroup's K sums belong to one channel (group): a thread adds its own terms in its own fixed order, the 64
+// lanes of a wave by an xor shuffle tree (32, 16, .. 1), the waves in wave order through LDS, and the workgroup stores its K
+// partials with plain stores, each word exactly once (block_sums_store).  launch_sums_reduce then adds a channel's partials
+// in index order.  No float atomics, and the grids are functions of the shape alone: every sum has one order.
+#pragma once
+#include "cdn_common.h"
+
+namespace cdn {
+
+// grad_w [C][K - 1] and grad_b [C] (either may be NULL) from the workgroups' partials
+// [outer][C / G][chunks][G][K] -- K sums per channel: K - 1 taps and the bias, G channels per workgroup -- summed outer
+// index first, then chunks, both ascending.  Defined in codenet_heads_train.hip.
+int launch_sums_reduce(const float *part, float *grad_w, float *grad_b, int C, int G, int K, int outer, int chunks,
+                       hipStream_t st, const char *what);
+
+#ifdef __HIPCC__
+// scale, zero point and RN(1 / scale) of a QuantAct state (snapshot): the operands of fake_quant_r
+struct Fq {
+  float s, z, r;
+};
+__device__ __forceinline__ Fq load_fq(const unsigned *__restrict__ state) {
+  Fq f;
+  f.s = reinterpret_cast<const float *>(state)[2];
+  f.z = reinterpret_cast<const float *>(state)[3];
+  f.r = __fdiv_rn(1.0f, f.s);
+  return f;
+}
+__device__ __forceinline__ float fq_relu(float v, const Fq &f) { return fake_quant_r(relu_keep_nan(v), f.s, f.z, f.r); }
+
+// NC columns xa - LEAD .. xa - LEAD + NC - 1 of row y of an H x W plane: v[j], 0.0f where the column (or the whole row)
+// lies outside the plane; returns the mask of the columns inside.  xa is a multiple of 4 inside the row: 0 <= xa < W (a
+// live item's first quad; only the quads behind it are tested).  VEC: W % 4 == 0 and 16-byte aligned rows, so a quad that
+// starts inside the plane ends inside it.
+template <int NC, int LEAD, bool VEC>
+__device__ __forceinline__ unsigned load_cols(const float *__restrict__ plane, int y, int H, int W, int xa,
+                                              float (&v)[NC]) {
+#pragma unroll
+  for (int j = 0; j < NC; ++j) v[j] = 0.0f;
+  if (y < 0 || y >= H) return 0u;
+  const float *row = plane + (long)y * W;
+  unsigned ok = 0u;
+  if (VEC) {
+    constexpr int NV = (NC - LEAD) / 4;
+    if (LEAD && xa > 0) { v[0] = row[xa - 1]; ok |= 1u; }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      if (k == 0 || xa + 4 * k < W) {
+        const float4 c = *reinterpret_cast<const float4 *>(row + xa + 4 * k);
+        v[LEAD + 4 * k] = c.x; v[LEAD + 4 * k + 1] = c.y; v[LEAD + 4 * k + 2] = c.z; v[LEAD + 4 * k + 3] = c.w;
+        ok |= 0xfu << (LEAD + 4 * k);
+      }
+    }
+#pragma unroll
+    for (int j = LEAD + 4 * NV; j < NC; ++j) {
+      const int x = xa - LEAD + j;
+      if (x < W) { v[j] = row[x]; ok |= 1u << j; }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < NC; ++j) {
+      const int x = xa - LEAD + j;
+      if (x >= 0 && x < W) { v[j] = row[x]; ok |= 1u << j; }
+    }
+  }
+  return ok;
+}
+
+// columns x0 .. x0 + 3 of a row of width W; VEC: one 16-byte store where the quad starts inside the row
+template <bool VEC>
+__device__ __forceinline__ void store4(float *__restrict__ row, int W, int x0, const float (&v)[4]) {
+  if (VEC) {
+    if (x0 < W) *reinterpret_cast<float4 *>(row + x0) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (x0 + i < W) row[x0 + i] = v[i];
+  }
+}
+
+// One window row of a depthwise input (columns xa - 1 ..).  RQ: the stored values are pre-activation, a = fq(relu(v)) is
+// formed here and the returned mask is v > 0 (the ReLU mask of the backward); !RQ: final values, read as they are.  Taps
+// outside the plane are literal zeros (the convolution's padding).
+template <int NC, bool RQ, bool VEC>
+__device__ __forceinline__ unsigned load_act(const float *__restrict__ plane, int y, int H, int W, int xa, const Fq &f,
+                                             float (&a)[NC]) {
+  float v[NC];
+  const unsigned ok = load_cols<NC, 1, VEC>(plane, y, H, W, xa, v);
+  unsigned pos = 0u;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const bool in = (ok >> j) & 1u;
+    if (RQ) {
+      a[j] = in ? fake_quant_r(relu_keep_nan(v[j]), f.s, f.z, f.r) : 0.0f;
+      pos |= (in && v[j] > 0.0f) ? (1u << j) : 0u;
+    } else {
+      a[j] = v[j];
+    }
+  }
+  return RQ ? pos : ok;
+}
+
+// The end of a weight-gradient kernel (see the head of the file); every thread of the workgroup calls it.  red: K floats
+// of LDS per wave; part [workgroups][K]: workgroup blockIdx.x stores its K words.
+template <int K>
+__device__ __forceinline__ void block_sums_store(const float (&sums)[K], float *red, float *__restrict__ part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    float v = sums[k];
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    if (lane == 0) red[wave * K + k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    float s = red[threadIdx.x];
+    for (int i = 1; i < nw; ++i) s += red[i * K + threadIdx.x];
+    part[(long)blockIdx.x * K + threadIdx.x] = s;
+  }
+}
+#endif
+
+}  // namespace cdn

@@ -14,7 +14,7 @@
 // threads own consecutive column quads of a row (one 16-byte load each where the rows are 16-byte aligned, scalar loads
 // for ragged widths and misaligned pointers), then consecutive strips.  No LDS tiles, no scratch: occupancy hides the
 // latency of these bandwidth-bound kernels.
-#include "cdn_common.h"
+#include "cdn_train.h"
 
 #include <algorithm>
 
@@ -23,69 +23,8 @@ namespace {
 constexpr int kHdRows = 8;      // rows of a thread's strip
 constexpr int kHdSums = 10;     // per-channel sums of the backward: nine taps of grad_w2 and grad_b2
 
-struct Fq {
-  float s, z, r;
-};
-__device__ __forceinline__ Fq load_fq(const unsigned *__restrict__ state) {
-  Fq f;
-  f.s = reinterpret_cast<const float *>(state)[2];
-  f.z = reinterpret_cast<const float *>(state)[3];
-  f.r = __fdiv_rn(1.0f, f.s);
-  return f;
-}
-
-// Columns x0 - 1 .. x0 + 4 of one row of a plane: v[j], 0.0f where the column (or the whole row) lies outside the plane;
-// returns the mask of the columns inside.  VEC: W % 4 == 0 and 16-byte aligned rows, so x0 + 3 < W.
-template <bool VEC>
-__device__ __forceinline__ unsigned load6(const float *__restrict__ plane, int y, int H, int W, int x0, float (&v)[6]) {
-#pragma unroll
-  for (int j = 0; j < 6; ++j) v[j] = 0.0f;
-  if (y < 0 || y >= H) return 0u;
-  const float *row = plane + (long)y * W;
-  unsigned ok = 0u;
-  if (VEC) {
-    const float4 c = *reinterpret_cast<const float4 *>(row + x0);
-    v[1] = c.x; v[2] = c.y; v[3] = c.z; v[4] = c.w;
-    ok = 0x1eu;
-    if (x0 > 0) { v[0] = row[x0 - 1]; ok |= 1u; }
-    if (x0 + 4 < W) { v[5] = row[x0 + 4]; ok |= 0x20u; }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int x = x0 - 1 + j;
-      if (x >= 0 && x < W) { v[j] = row[x]; ok |= 1u << j; }
-    }
-  }
-  return ok;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float *__restrict__ plane, int y, int W, int x0, const float (&v)[4]) {
-  float *row = plane + (long)y * W;
-  if (VEC) {
-    *reinterpret_cast<float4 *>(row + x0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (x0 + i < W) row[x0 + i] = v[i];
-  }
-}
-
-// a1 = fq1(relu(y1)) of one window row; taps outside the plane are literal zeros (the convolution's padding)
-template <bool VEC>
-__device__ __forceinline__ unsigned load_a1(const float *__restrict__ plane, int y, int H, int W, int x0, const Fq &f,
-                                            float (&a)[6]) {
-  float v[6];
-  const unsigned ok = load6<VEC>(plane, y, H, W, x0, v);
-  unsigned pos = 0u;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const bool in = (ok >> j) & 1u;
-    a[j] = in ? cdn::fake_quant_r(cdn::relu_keep_nan(v[j]), f.s, f.z, f.r) : 0.0f;
-    pos |= (in && v[j] > 0.0f) ? (1u << j) : 0u;
-  }
-  return pos;      // the ReLU mask y1 > 0 of the row
-}
+using cdn::Fq;
+using cdn::load_fq;
 
 // ------------------------------------------------------------------------------------------------------
 // head_dw_fwd_kernel: r2 = relu(dw3x3(fq1(relu(y1)), w2) + b2), stored BEFORE quantisation (its consumers fake-quantise
@@ -117,10 +56,10 @@ head_dw_fwd_kernel(const float *__restrict__ y1, const unsigned *__restrict__ a1
     for (int k = 0; k < 9; ++k) w[k] = w2[c * 9 + k];
     const float bias = b2 ? b2[c] : 0.0f;
     float a[3][6];
-    load_a1<VEC>(src, ya - 1, H, W, x0, f, a[0]);
-    load_a1<VEC>(src, ya, H, W, x0, f, a[1]);
+    cdn::load_act<6, true, VEC>(src, ya - 1, H, W, x0, f, a[0]);
+    cdn::load_act<6, true, VEC>(src, ya, H, W, x0, f, a[1]);
     for (int y = ya; y < yb; ++y) {
-      load_a1<VEC>(src, y + 1, H, W, x0, f, a[2]);
+      cdn::load_act<6, true, VEC>(src, y + 1, H, W, x0, f, a[2]);
       float out[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -137,7 +76,7 @@ head_dw_fwd_kernel(const float *__restrict__ y1, const unsigned *__restrict__ a1
           has_nan |= (v != v);
         }
       }
-      store4<VEC>(dst, y, W, x0, out);
+      cdn::store4<VEC>(dst + (long)y * W, W, x0, out);
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         a[0][j] = a[1][j];
@@ -209,9 +148,8 @@ head_tail_fwd_kernel(const float *__restrict__ r2, const unsigned *__restrict__ 
 //   g_y1[q] = [y1[q] > 0] . sum_t W2q[c][t] g_y2[q - t]        a GATHER over the nine neighbours with mirrored taps
 //   g_W2q[c][t] = sum_{n,p} g_y2[p] a1[p + t],  g_b2[c] = sum_{n,p} g_y2[p],  a1 = fq1(relu(y1)) recomputed on load
 // A workgroup works on ONE (n, c) plane (chunk blockIdx.x % chunks of its strips), so its ten sums belong to one channel:
-// a thread sums its own pixels in row-major order, the 64 lanes of a wave by an xor shuffle tree, the waves in wave order
-// through LDS, and the workgroup stores its ten partials -- plain stores, each word exactly once, no atomics.
-// head_dw_bwd_reduce_kernel sums the partials of a channel in index order (images, then chunks).
+// a thread sums its own pixels in row-major order, then cdn::block_sums_store; the partials [N][C][chunks][10] of a
+// channel are added in index order (images, then chunks) by cdn::launch_sums_reduce (cdn_train.h).
 // g_y1 goes to gy1 + n * gy1_pitch + c * H * W: a channel slice of a wider [N][heads * C][H][W] buffer.
 // ------------------------------------------------------------------------------------------------------
 template <int CO, bool VEC>
@@ -220,7 +158,7 @@ head_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ w3, co
                    const float *__restrict__ y1, const unsigned *__restrict__ a1_state, const float *__restrict__ w2,
                    float *__restrict__ gy1, long gy1_pitch, float *__restrict__ part, int C, int H, int W, int wq,
                    int strips, int chunks) {
-  __shared__ float red[4][kHdSums];
+  __shared__ float red[4 * kHdSums];
   const int chunk = (int)(blockIdx.x % chunks);
   const long plane = blockIdx.x / chunks;
   const int n = (int)(plane / C), c = (int)(plane % C);
@@ -245,21 +183,21 @@ head_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ w3, co
     // one window row: g_y2 (masked by r2 > 0), a1 and the mask y1 > 0
     auto load_row = [&](int y, float (&gr)[6], float (&ar)[6], unsigned &pm) {
       float rr[6], gv[6];
-      const unsigned ok = load6<VEC>(rsrc, y, H, W, x0, rr);
+      const unsigned ok = cdn::load_cols<6, 1, VEC>(rsrc, y, H, W, x0, rr);
       if (CO == 0) {
-        load6<VEC>(gsrc, y, H, W, x0, gv);
+        cdn::load_cols<6, 1, VEC>(gsrc, y, H, W, x0, gv);
       } else {
 #pragma unroll
         for (int o = 0; o < CO; ++o) {
           float t[6];
-          load6<VEC>(gsrc + (long)o * HW, y, H, W, x0, t);
+          cdn::load_cols<6, 1, VEC>(gsrc + (long)o * HW, y, H, W, x0, t);
 #pragma unroll
           for (int j = 0; j < 6; ++j) gv[j] = o == 0 ? w3c[0] * t[j] : fmaf(w3c[o], t[j], gv[j]);
         }
       }
 #pragma unroll
       for (int j = 0; j < 6; ++j) gr[j] = (((ok >> j) & 1u) && rr[j] > 0.0f) ? gv[j] : 0.0f;
-      pm = load_a1<VEC>(ysrc, y, H, W, x0, f, ar);
+      pm = cdn::load_act<6, true, VEC>(ysrc, y, H, W, x0, f, ar);
     };
     load_row(ya - 1, gw[0], aw[0], pos[0]);
     load_row(ya, gw[1], aw[1], pos[1]);
@@ -283,7 +221,7 @@ head_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ w3, co
           sums[9] += gc;
         }
       }
-      store4<VEC>(dst, y, W, x0, out);
+      cdn::store4<VEC>(dst + (long)y * W, W, x0, out);
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         gw[0][j] = gw[1][j]; gw[1][j] = gw[2][j];
@@ -293,36 +231,25 @@ head_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ w3, co
       pos[1] = pos[2];
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int k = 0; k < kHdSums; ++k) {
-    float v = sums[k];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kHdSums) {
-    float s = red[0][threadIdx.x];
-    for (int i = 1; i < nw; ++i) s += red[i][threadIdx.x];
-    part[(long)blockIdx.x * kHdSums + threadIdx.x] = s;
-  }
+  cdn::block_sums_store(sums, red, part);
 }
 
-// grad_w2 [C][9] and grad_b2 [C] from the workgroups' partials [N][C][chunks][10], summed in index order
+// grad_w [C][K - 1] and grad_b [C] of the training kernels from their workgroups' partials (cdn_train.h): one thread per
+// (channel, k), the partials of its sum added in index order
 __global__ void __launch_bounds__(256)
-head_dw_bwd_reduce_kernel(const float *__restrict__ part, float *__restrict__ gw2, float *__restrict__ gb2, int N, int C,
-                          int chunks) {
+train_sums_reduce_kernel(const float *__restrict__ part, float *__restrict__ gw, float *__restrict__ gb, int C, int G, int K,
+                         int outer, long outer_stride, int chunks, long chunk_stride) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * kHdSums) return;
-  const int c = i / kHdSums, k = i % kHdSums;
+  if (i >= C * K) return;
+  const int c = i / K, k = i % K;
+  const float *src = part + (long)(c / G) * chunks * chunk_stride + (c % G) * K + k;
   float s = 0.0f;
-  for (int n = 0; n < N; ++n)
-    for (int h = 0; h < chunks; ++h) s += part[(((long)n * C + c) * chunks + h) * kHdSums + k];
-  if (k < 9) {
-    if (gw2) gw2[c * 9 + k] = s;
-  } else if (gb2) {
-    gb2[c] = s;
+  for (int o = 0; o < outer; ++o)
+    for (int h = 0; h < chunks; ++h) s += src[o * outer_stride + h * chunk_stride];
+  if (k < K - 1) {
+    if (gw) gw[c * (K - 1) + k] = s;
+  } else if (gb) {
+    gb[c] = s;
   }
 }
 
@@ -338,9 +265,16 @@ HdPlan head_plan(int64_t H, int64_t W) {
   p.chunks = (int)cdn::ceil_div(items, p.threads);
   return p;
 }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
+
+int cdn::launch_sums_reduce(const float *part, float *grad_w, float *grad_b, int C, int G, int K, int outer, int chunks,
+                            hipStream_t st, const char *what) {
+  const long chunk_stride = (long)G * K, outer_stride = (long)(C / G) * chunks * chunk_stride;
+  train_sums_reduce_kernel<<<(unsigned)cdn::ceil_div((int64_t)C * K, 256), 256, 0, st>>>(part, grad_w, grad_b, C, G, K, outer,
+                                                                                         outer_stride, chunks, chunk_stride);
+  return cdn::check_launch(what);
+}
 
 extern "C" int cdn_codenet_head_act_update(float *x_min, float *x_max, void *state, const float *partials,
                                            int64_t n_partials, int bits, double momentum, int running, int relu,
@@ -363,16 +297,12 @@ extern "C" int cdn_codenet_head_dw_forward(const float *y1, const void *a1_state
   CDN_REQUIRE(y1 && a1_state && w2 && r2, CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, CDN_ERR_ARG, "non-positive size");
   CDN_REQUIRE(N * C * H * W < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
-  cdn::QUpdate qu = cdn::no_qupdate();
-  if (running) {
-    CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");
-    CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
-    qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
-  }
+  cdn::QUpdate qu;
+  if (int rc = cdn::tracked_qupdate(&qu, x_min, x_max, state, counters, bits, momentum, running)) return rc;
   const HdPlan p = head_plan(H, W);
   const long items = (long)(N * C) * p.strips * p.wq;
   const unsigned grid = (unsigned)cdn::ceil_div(items, 256);
-  const bool vec = (W & 3) == 0 && aligned16(y1) && aligned16(r2);
+  const bool vec = (W & 3) == 0 && cdn::aligned16(y1) && cdn::aligned16(r2);
   const unsigned *a1s = static_cast<const unsigned *>(a1_state);
   unsigned *copy = running ? static_cast<unsigned *>(state_copy) : nullptr;
   hipStream_t st = cdn::as_stream(stream);
@@ -394,7 +324,7 @@ extern "C" int cdn_codenet_head_tail_train_forward(const float *r2, const void *
   const int hq = (int)cdn::ceil_div(HW, 4);
   const long items = (long)N * hq;
   const unsigned grid = (unsigned)cdn::ceil_div(items, 256);
-  const bool vec = (HW & 3) == 0 && aligned16(r2) && aligned16(y3);
+  const bool vec = (HW & 3) == 0 && cdn::aligned16(r2) && cdn::aligned16(y3);
   const unsigned *a2s = static_cast<const unsigned *>(a2_state);
   hipStream_t st = cdn::as_stream(stream);
 #define CDN_TAIL(CO)                                                                                              \
@@ -413,7 +343,7 @@ extern "C" int cdn_codenet_head_tail_train_forward(const float *r2, const void *
 extern "C" size_t cdn_codenet_head_dw_backward_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W) {
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
   const HdPlan p = head_plan(H, W);
-  return ((size_t)N * (size_t)C * (size_t)p.chunks * kHdSums * sizeof(float) + 255) / 256 * 256;
+  return cdn::round256((size_t)N * (size_t)C * (size_t)p.chunks * kHdSums * sizeof(float));
 }
 
 extern "C" int cdn_codenet_head_dw_backward(const float *g, const float *w3, int64_t Co, const float *r2, const float *y1,
@@ -430,11 +360,10 @@ extern "C" int cdn_codenet_head_dw_backward(const float *g, const float *w3, int
               "shape too large");
   const HdPlan p = head_plan(H, W);
   CDN_REQUIRE(N * C * p.chunks < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
-  CDN_REQUIRE(workspace_bytes >= cdn_codenet_head_dw_backward_workspace_bytes(N, C, H, W) &&
-                  (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-              CDN_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
-  const bool vec = (W & 3) == 0 && (grad_y1_image_pitch & 3) == 0 && aligned16(g) && aligned16(r2) && aligned16(y1) &&
-                   aligned16(grad_y1);
+  if (int rc = cdn::check_workspace(workspace, workspace_bytes, cdn_codenet_head_dw_backward_workspace_bytes(N, C, H, W)))
+    return rc;
+  const bool vec = (W & 3) == 0 && (grad_y1_image_pitch & 3) == 0 && cdn::aligned16(g) && cdn::aligned16(r2) && cdn::aligned16(y1) &&
+                   cdn::aligned16(grad_y1);
   const unsigned grid = (unsigned)(N * C * p.chunks);
   const unsigned *a1s = static_cast<const unsigned *>(a1_state);
   float *part = static_cast<float *>(workspace);
@@ -457,7 +386,6 @@ extern "C" int cdn_codenet_head_dw_backward(const float *g, const float *w3, int
 #undef CDN_HBWD
   int rc = cdn::check_launch("codenet head depthwise backward");
   if (rc || !(grad_w2 || grad_b2)) return rc;
-  head_dw_bwd_reduce_kernel<<<(unsigned)cdn::ceil_div(C * kHdSums, 256), 256, 0, st>>>(part, grad_w2, grad_b2, (int)N,
-                                                                                       (int)C, p.chunks);
-  return cdn::check_launch("codenet head depthwise backward reduce");
+  return cdn::launch_sums_reduce(part, grad_w2, grad_b2, (int)C, 1, kHdSums, (int)N, p.chunks, st,
+                                 "codenet head depthwise backward reduce");
 }

@@ -25,8 +25,6 @@ constexpr int kSlab = 8;                 // doubles per workgroup: pos, neg, num
 // (the result block is 8 floats: loss, hm_loss, wh_loss, off_loss, hm denominator, reg denominator, num_pos, mask sum)
 constexpr int kMaxObjs = 2048;           // target kernel: one 24-byte LDS record per object row
 
-inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
 inline int hm_blocks(int64_t total) {
   const int64_t quads = (total + 3) / 4;
   const int64_t nb = ceil_div(quads, kThreads);

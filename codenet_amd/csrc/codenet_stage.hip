@@ -1511,18 +1511,14 @@ extern "C" int cdn_codenet_dw_forward_range(const float *x, const float *s, cons
 // the fused inference schedule's protocol) -- no cdn_quantact_forward_partials update launch, no state-copy launch.
 // counters: cdn_quantact_arrive_words() zero-initialised 32-bit words per QuantAct (left zero by every call);
 // state_copy (8 words, may be NULL): the state after the update, for the backward pass.
-#define CDN_REQUIRE_UPDATE()                                                                                          \
-  CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");                             \
-  CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits)
-
 extern "C" int cdn_quantact_arrive_words(void) { return cdn::kArriveWords; }
 
 extern "C" int cdn_codenet_scale_forward_update(const float *x, const float *w_scale, const float *b_scale, float *s,
                                                 int64_t N, int64_t C, int64_t H, int64_t W, float lo, float hi,
                                                 float *x_min, float *x_max, void *state, void *counters, int bits,
                                                 double momentum, void *state_copy, void *stream) {
-  CDN_REQUIRE_UPDATE();
-  const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
+  cdn::QUpdate qu;
+  if (int rc = cdn::tracked_qupdate(&qu, x_min, x_max, state, counters, bits, momentum)) return rc;
   return scale_forward_impl(x, w_scale, b_scale, s, N, C, H, W, lo, hi, nullptr, stream, &qu,
                             static_cast<unsigned *>(state_copy));
 }
@@ -1538,8 +1534,8 @@ extern "C" int cdn_codenet_dw_forward_update(const float *x, const float *s, con
                                              int64_t C, int64_t H, int64_t W, int up2, float *x_min, float *x_max,
                                              void *state, void *counters, int bits, double momentum, void *state_copy,
                                              void *stream) {
-  CDN_REQUIRE_UPDATE();
-  const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
+  cdn::QUpdate qu;
+  if (int rc = cdn::tracked_qupdate(&qu, x_min, x_max, state, counters, bits, momentum)) return rc;
   unsigned *copy = static_cast<unsigned *>(state_copy);
   // (up2: x, s are the STORED tensors, H x W the up-sampled resolution -- cdn_codenet_dw_up2_forward's convention)
   if (up2) return dw_up2_forward_impl(x, s, w_dw, d, N, C, H, W, nullptr, stream, &qu, copy);

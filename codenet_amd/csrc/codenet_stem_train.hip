@@ -13,10 +13,10 @@
 // channels x a CHUNK of 256 * P consecutive output positions (n, oy, ox flattened; P = clamp(positions / 1024, 1, 8)):
 // grid = 6 groups x chunks.  A thread takes the positions chunk_start + t + 256 k, k < P, in that order: it loads the 27
 // image taps of the position once (guarded, zero outside the image) and the four gradients, and adds 4 x 28 products into
-// registers.  Then one order: the 64 lanes by an xor shuffle tree, the waves in wave order through LDS, plain stores of the
-// workgroup's 112 partials, and stem_wgrad_reduce_kernel adds a channel's partials in chunk order.  No float atomics; the grid
-// is a function of the shape alone.  The image patch is read once per channel group, six times in all, through L2.
-#include "cdn_common.h"
+// registers.  Then cdn::block_sums_store with the workgroup's 112 sums, and cdn::launch_sums_reduce adds a channel's partials
+// in chunk order (cdn_train.h).  No float atomics; the grid is a function of the shape alone.  The image patch is read once
+// per channel group, six times in all, through L2.
+#include "cdn_train.h"
 
 #include <algorithm>
 
@@ -28,19 +28,9 @@ constexpr int kStGroup = 4;                       // output channels per workgro
 constexpr int kStSums = kStTaps + 1;              // per channel: 27 taps of grad_w and grad_b
 constexpr int kStPart = kStGroup * kStSums;       // partial sums a workgroup stores
 
-struct Fq {
-  float s, z, r;
-};
-__device__ __forceinline__ Fq load_fq(const unsigned *__restrict__ state) {
-  Fq f;
-  f.s = reinterpret_cast<const float *>(state)[2];
-  f.z = reinterpret_cast<const float *>(state)[3];
-  f.r = __fdiv_rn(1.0f, f.s);
-  return f;
-}
-__device__ __forceinline__ float fq_relu(float v, const Fq &f) {
-  return cdn::fake_quant_r(cdn::relu_keep_nan(v), f.s, f.z, f.r);
-}
+using cdn::Fq;
+using cdn::fq_relu;
+using cdn::load_fq;
 
 // the 27 taps of output position (oy, ox) of image n in (ci, dy, dx) order, zero outside the image
 __device__ __forceinline__ void load_patch(const float *__restrict__ img, int n, int oy, int ox, int H, int W, int stride,
@@ -217,15 +207,13 @@ __global__ void __launch_bounds__(256)
 stem_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ y0, const float *__restrict__ img,
                   float *__restrict__ part, int H, int W, int Ho, int Wo, int stride, int chunks, int per_thread,
                   long positions) {
-  __shared__ float red[4][kStPart];
+  __shared__ float red[4 * kStPart];
   const int grp = (int)(blockIdx.x / chunks);
   const long start = (long)(blockIdx.x % chunks) * 256 * per_thread;
   const int HW = Ho * Wo;
-  float sums[kStGroup][kStSums];
+  float sums[kStPart];      // [kStGroup][kStSums]
 #pragma unroll
-  for (int e = 0; e < kStGroup; ++e)
-#pragma unroll
-    for (int k = 0; k < kStSums; ++k) sums[e][k] = 0.0f;
+  for (int k = 0; k < kStPart; ++k) sums[k] = 0.0f;
   for (int it = 0; it < per_thread; ++it) {
     const long pidx = start + (long)it * 256 + threadIdx.x;
     if (pidx < positions) {
@@ -239,43 +227,12 @@ stem_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ y0, con
         float gv = g[o + (long)e * HW];
         if (y0) gv = y0[o + (long)e * HW] > 0.0f ? gv : 0.0f;
 #pragma unroll
-        for (int k = 0; k < kStTaps; ++k) sums[e][k] = fmaf(gv, v[k], sums[e][k]);
-        sums[e][kStTaps] += gv;
+        for (int k = 0; k < kStTaps; ++k) sums[e * kStSums + k] = fmaf(gv, v[k], sums[e * kStSums + k]);
+        sums[e * kStSums + kStTaps] += gv;
       }
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int e = 0; e < kStGroup; ++e)
-#pragma unroll
-    for (int k = 0; k < kStSums; ++k) {
-      float s = sums[e][k];
-#pragma unroll
-      for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m, 64);
-      if (lane == 0) red[wave][e * kStSums + k] = s;
-    }
-  __syncthreads();
-  if (threadIdx.x < kStPart) {
-    float s = red[0][threadIdx.x];
-    for (int i = 1; i < 4; ++i) s += red[i][threadIdx.x];
-    part[(long)blockIdx.x * kStPart + threadIdx.x] = s;
-  }
-}
-
-// grad_w [24][27] and grad_b [24] from the partials [groups][chunks][4][28], summed in chunk order
-__global__ void __launch_bounds__(256)
-stem_wgrad_reduce_kernel(const float *__restrict__ part, float *__restrict__ gw, float *__restrict__ gb, int chunks) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= kStCo * kStSums) return;
-  const int c = i / kStSums, k = i % kStSums;
-  const float *src = part + (long)(c / kStGroup) * chunks * kStPart + (c % kStGroup) * kStSums + k;
-  float s = 0.0f;
-  for (int h = 0; h < chunks; ++h) s += src[(long)h * kStPart];
-  if (k < kStTaps) {
-    if (gw) gw[c * kStTaps + k] = s;
-  } else if (gb) {
-    gb[c] = s;
-  }
+  cdn::block_sums_store(sums, red, part);
 }
 
 struct StPlan {
@@ -304,12 +261,8 @@ extern "C" int cdn_codenet_stem_train_forward(const float *img, const float *w, 
   CDN_REQUIRE(stride == 2 || stride == 4, CDN_ERR_ARG, "stride must be 2 or 4, got %d", stride);
   const StPlan p = stem_plan(N, H, W, stride);
   CDN_REQUIRE(N * 3 * H * W < (1ll << 31) && N * kStCo * p.Ho * p.Wo < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
-  cdn::QUpdate qu = cdn::no_qupdate();
-  if (running) {
-    CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");
-    CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
-    qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
-  }
+  cdn::QUpdate qu;
+  if (int rc = cdn::tracked_qupdate(&qu, x_min, x_max, state, counters, bits, momentum, running)) return rc;
   const int chunks = (int)cdn::ceil_div((int64_t)p.Ho * p.Wo, 256);
   CDN_REQUIRE(N * (int64_t)chunks < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
   unsigned *copy = running ? static_cast<unsigned *>(state_copy) : nullptr;
@@ -347,7 +300,7 @@ extern "C" int cdn_codenet_stem_pool_backward(const float *g, const float *y0, c
 extern "C" size_t cdn_codenet_stem_backward_workspace_bytes(int64_t N, int64_t H, int64_t W, int stride) {
   if (N <= 0 || H <= 0 || W <= 0 || (stride != 2 && stride != 4)) return 0;
   const StPlan p = stem_plan(N, H, W, stride);
-  return ((size_t)(kStCo / kStGroup) * (size_t)p.chunks * kStPart * sizeof(float) + 255) / 256 * 256;
+  return cdn::round256((size_t)(kStCo / kStGroup) * (size_t)p.chunks * kStPart * sizeof(float));
 }
 
 extern "C" int cdn_codenet_stem_backward(const float *g, const float *y0, const float *img, float *grad_w, float *grad_b,
@@ -359,15 +312,14 @@ extern "C" int cdn_codenet_stem_backward(const float *g, const float *y0, const 
   CDN_REQUIRE(stride == 2 || stride == 4, CDN_ERR_ARG, "stride must be 2 or 4, got %d", stride);
   const StPlan p = stem_plan(N, H, W, stride);
   CDN_REQUIRE(N * 3 * H * W < (1ll << 31) && N * kStCo * p.Ho * p.Wo < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
-  CDN_REQUIRE(workspace_bytes >= cdn_codenet_stem_backward_workspace_bytes(N, H, W, stride) &&
-                  (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-              CDN_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
+  if (int rc = cdn::check_workspace(workspace, workspace_bytes, cdn_codenet_stem_backward_workspace_bytes(N, H, W, stride)))
+    return rc;
   float *part = static_cast<float *>(workspace);
   hipStream_t st = cdn::as_stream(stream);
   stem_wgrad_kernel<<<(unsigned)((kStCo / kStGroup) * p.chunks), 256, 0, st>>>(g, y0, img, part, (int)H, (int)W, p.Ho, p.Wo,
                                                                               stride, p.chunks, p.per_thread, p.positions);
   int rc = cdn::check_launch("codenet stem backward");
   if (rc || !(grad_w || grad_b)) return rc;
-  stem_wgrad_reduce_kernel<<<(unsigned)cdn::ceil_div(kStCo * kStSums, 256), 256, 0, st>>>(part, grad_w, grad_b, p.chunks);
-  return cdn::check_launch("codenet stem backward reduce");
+  return cdn::launch_sums_reduce(part, grad_w, grad_b, kStCo, kStGroup, kStSums, 1, p.chunks, st,
+                                 "codenet stem backward reduce");
 }

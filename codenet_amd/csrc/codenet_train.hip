@@ -430,7 +430,7 @@ WgPlan wgrad_plan(int64_t N, int64_t C, int64_t Co, int64_t HW) {
 extern "C" size_t cdn_codenet_pointwise_wgrad_workspace_bytes(int64_t N, int64_t C, int64_t Co, int64_t HW) {
   if (N <= 0 || C <= 0 || Co <= 0 || HW <= 0) return 0;
   const WgPlan p = wgrad_plan(N, C, Co, HW);
-  return ((size_t)p.nz * (size_t)Co * (size_t)(C + 1) * 4 + 255) / 256 * 256;   // weight tiles + bias rows
+  return cdn::round256((size_t)p.nz * (size_t)Co * (size_t)(C + 1) * 4);   // weight tiles + bias rows
 }
 
 static int pointwise_wgrad_impl(const float *grad_y, const float *d, const void *d_state, float *grad_w, float *grad_b,
@@ -443,9 +443,8 @@ static int pointwise_wgrad_impl(const float *grad_y, const float *d, const void 
   CDN_REQUIRE(N > 0 && C > 0 && Co > 0 && HW > 0, CDN_ERR_ARG, "non-positive size");
   CDN_REQUIRE(N * C * HW < (1ll << 31) && N * Co * HW < (1ll << 31) && C * Co < (1ll << 31),
               CDN_ERR_UNSUPPORTED, "shape too large");
-  CDN_REQUIRE(workspace_bytes >= cdn_codenet_pointwise_wgrad_workspace_bytes(N, C, Co, HW) &&
-                  (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-              CDN_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
+  if (int rc = cdn::check_workspace(workspace, workspace_bytes, cdn_codenet_pointwise_wgrad_workspace_bytes(N, C, Co, HW)))
+    return rc;
   CDN_REQUIRE((reinterpret_cast<uintptr_t>(grad_y) & 15) == 0 && (scalar_slice || (reinterpret_cast<uintptr_t>(d) & 15) == 0),
               CDN_ERR_ARG, "grad_y / d must be 16-byte aligned");
   hipStream_t st = cdn::as_stream(stream);
@@ -1247,16 +1246,16 @@ static bool pwn_plan(int64_t N, int64_t C, int64_t Co, int64_t HW, PwnPlan *p) {
   p->ks = (N * npb * p->ncg < 4096 && (C >> 5) >= 8) ? 4 : 1;
   p->grid_x = (unsigned)((p->ks == 4 ? npb : cdn::ceil_div(npb, 4)) * p->ncg);
   p->lds = p->ks == 4 ? (size_t)4 * p->tn * 8 * 32 * 16 : 256;
-  const size_t codes = ((size_t)C * p->cot + 255) / 256 * 256;
+  const size_t codes = cdn::round256((size_t)C * p->cot);
   p->off_scale = codes;
-  p->off_sum = codes + ((size_t)p->cot * 4 + 255) / 256 * 256;
+  p->off_sum = codes + cdn::round256((size_t)p->cot * 4);
   p->dtn = C <= 128 ? 4 : 8;
   p->dncg = (int)cdn::ceil_div(C, 32 * p->dtn);
   p->ct = 32 * p->dtn * p->dncg;
   const size_t S = (size_t)(std::max<int64_t>(Co, p->cot) + 15) / 16;      // (the prep kernel's workgroups: 16 columns each)
-  p->off_wt = p->off_sum + ((size_t)p->cot * 4 + 255) / 256 * 256;
-  p->off_rws = p->off_wt + (S * p->ct * 32 + 255) / 256 * 256;
-  p->bytes = p->off_rws + (S * 16 * 4 + 255) / 256 * 256;
+  p->off_wt = p->off_sum + cdn::round256((size_t)p->cot * 4);
+  p->off_rws = p->off_wt + cdn::round256(S * p->ct * 32);
+  p->bytes = p->off_rws + cdn::round256(S * 16 * 4);
   return true;
 }
 
@@ -1295,9 +1294,8 @@ extern "C" int cdn_codenet_pointwise_i8_forward_update(const float *d, const voi
                                                        int64_t HW, void *workspace, size_t workspace_bytes,
                                                        int relu_range, float *x_min, float *x_max, void *state,
                                                        void *counters, int bits, double momentum, void *stream) {
-  CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");
-  CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
-  const cdn::QUpdate qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
+  cdn::QUpdate qu;
+  if (int rc = cdn::tracked_qupdate(&qu, x_min, x_max, state, counters, bits, momentum)) return rc;
   return pointwise_i8_forward_impl(d, d_state, w_q, bias, y, N, C, Co, HW, nullptr, workspace, workspace_bytes, stream,
                                    qu, relu_range);
 }

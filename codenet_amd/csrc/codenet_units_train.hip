@@ -18,7 +18,7 @@
 // 512 items, two workgroups per channel, 464 workgroups at 232 channels) and its ten partial sums of the backward still
 // belong to one channel.  The grid is a function of the shape alone, so every order is fixed.  No LDS tiles, no scratch:
 // the neighbours' rows come from L2 and occupancy hides the latency of these bandwidth-bound kernels.
-#include "cdn_common.h"
+#include "cdn_train.h"
 
 #include <algorithm>
 
@@ -26,86 +26,8 @@ namespace {
 
 constexpr int kUnSums = 10;     // per-channel sums of the backward: nine taps of grad_w and grad_b
 
-struct Fq {
-  float s, z, r;
-};
-__device__ __forceinline__ Fq load_fq(const unsigned *__restrict__ state) {
-  Fq f;
-  f.s = reinterpret_cast<const float *>(state)[2];
-  f.z = reinterpret_cast<const float *>(state)[3];
-  f.r = __fdiv_rn(1.0f, f.s);
-  return f;
-}
-
-// NC columns xa - LEAD .. xa - LEAD + NC - 1 of row y of an H x W plane: v[j], 0.0f where the column (or the whole row)
-// lies outside the plane; returns the mask of the columns inside.  xa is a multiple of 4.  VEC: W % 4 == 0 and 16-byte
-// aligned rows, so a quad that starts inside the plane ends inside it.
-template <int NC, int LEAD, bool VEC>
-__device__ __forceinline__ unsigned load_row(const float *__restrict__ plane, int y, int H, int W, int xa,
-                                             float (&v)[NC]) {
-#pragma unroll
-  for (int j = 0; j < NC; ++j) v[j] = 0.0f;
-  if (y < 0 || y >= H) return 0u;
-  const float *row = plane + (long)y * W;
-  unsigned ok = 0u;
-  if (VEC) {
-    constexpr int NV = (NC - LEAD) / 4;
-    if (LEAD && xa > 0) { v[0] = row[xa - 1]; ok |= 1u; }
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      if (xa + 4 * k < W) {
-        const float4 c = *reinterpret_cast<const float4 *>(row + xa + 4 * k);
-        v[LEAD + 4 * k] = c.x; v[LEAD + 4 * k + 1] = c.y; v[LEAD + 4 * k + 2] = c.z; v[LEAD + 4 * k + 3] = c.w;
-        ok |= 0xfu << (LEAD + 4 * k);
-      }
-    }
-#pragma unroll
-    for (int j = LEAD + 4 * NV; j < NC; ++j) {
-      const int x = xa - LEAD + j;
-      if (x < W) { v[j] = row[x]; ok |= 1u << j; }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < NC; ++j) {
-      const int x = xa - LEAD + j;
-      if (x >= 0 && x < W) { v[j] = row[x]; ok |= 1u << j; }
-    }
-  }
-  return ok;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float *__restrict__ row, int W, int x0, const float (&v)[4]) {
-  if (VEC) {
-    if (x0 < W) *reinterpret_cast<float4 *>(row + x0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (x0 + i < W) row[x0 + i] = v[i];
-  }
-}
-
-// One window row of the depthwise input.  RQ: the stored values are pre-activation, a = fq(relu(v)) is formed here and
-// the returned mask is v > 0 (the ReLU mask of the backward); !RQ: final values, read as they are.  Taps outside the
-// plane are literal zeros (the convolution's padding).
-template <int NC, bool RQ, bool VEC>
-__device__ __forceinline__ unsigned load_in(const float *__restrict__ plane, int y, int H, int W, int xa, const Fq &f,
-                                            float (&a)[NC]) {
-  float v[NC];
-  const unsigned ok = load_row<NC, 1, VEC>(plane, y, H, W, xa, v);
-  unsigned pos = 0u;
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    const bool in = (ok >> j) & 1u;
-    if (RQ) {
-      a[j] = in ? cdn::fake_quant_r(cdn::relu_keep_nan(v[j]), f.s, f.z, f.r) : 0.0f;
-      pos |= (in && v[j] > 0.0f) ? (1u << j) : 0u;
-    } else {
-      a[j] = v[j];
-    }
-  }
-  return RQ ? pos : ok;
-}
+using cdn::Fq;
+using cdn::load_fq;
 
 // the item of a thread: channel, image, first output row, first output column
 struct Item {
@@ -153,14 +75,14 @@ unit_dw_fwd_kernel(const float *__restrict__ in, long in_pitch, const unsigned *
     for (int k = 0; k < 9; ++k) wt[k] = w[c * 9 + k];
     const float bias = b ? b[c] : 0.0f;
     float a[3][NC];
-    load_in<NC, RQ, VEC>(src, S * ya - 1, H, W, S * x0, f, a[0]);
-    if (S == 1) load_in<NC, RQ, VEC>(src, ya, H, W, x0, f, a[1]);
+    cdn::load_act<NC, RQ, VEC>(src, S * ya - 1, H, W, S * x0, f, a[0]);
+    if (S == 1) cdn::load_act<NC, RQ, VEC>(src, ya, H, W, x0, f, a[1]);
     for (int y = ya; y < yb; ++y) {
       if (S == 1) {
-        load_in<NC, RQ, VEC>(src, y + 1, H, W, x0, f, a[2]);
+        cdn::load_act<NC, RQ, VEC>(src, y + 1, H, W, x0, f, a[2]);
       } else {
-        load_in<NC, RQ, VEC>(src, S * y, H, W, S * x0, f, a[1]);
-        load_in<NC, RQ, VEC>(src, S * y + 1, H, W, S * x0, f, a[2]);
+        cdn::load_act<NC, RQ, VEC>(src, S * y, H, W, S * x0, f, a[1]);
+        cdn::load_act<NC, RQ, VEC>(src, S * y + 1, H, W, S * x0, f, a[2]);
       }
       float o[4];
 #pragma unroll
@@ -178,7 +100,7 @@ unit_dw_fwd_kernel(const float *__restrict__ in, long in_pitch, const unsigned *
           has_nan |= (v != v);
         }
       }
-      store4<VEC>(dst + (long)y * Wo, Wo, x0, o);
+      cdn::store4<VEC>(dst + (long)y * Wo, Wo, x0, o);
 #pragma unroll
       for (int j = 0; j < NC; ++j) {
         if (S == 1) {
@@ -207,9 +129,8 @@ unit_dw_fwd_kernel(const float *__restrict__ in, long in_pitch, const unsigned *
 // input pixel is written exactly once (odd planes: the row / column past the edge is skipped).  g_in goes to
 // gin + n * gin_pitch + c * H * W (a channel slice of a wider buffer); ACC: added to what is stored there (the second of
 // the two contributions to a stride-2 unit's grad_x).  gin == NULL: only the weight / bias gradient.
-// Sums: a thread adds its own outputs in row-major order, the 64 lanes of a wave by an xor shuffle tree, the waves in
-// wave order through LDS; the workgroup stores its ten partials -- plain stores, each word exactly once, no atomics.
-// unit_dw_bwd_reduce_kernel sums the partials of a channel in chunk order.
+// Sums: a thread adds its own outputs in row-major order, then cdn::block_sums_store; the partials [C][chunks][10] of a
+// channel are added in chunk order by cdn::launch_sums_reduce (cdn_train.h).
 // ------------------------------------------------------------------------------------------------------
 template <int S, bool RQ, bool VEC>
 __global__ void __launch_bounds__(256)
@@ -219,7 +140,7 @@ unit_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ in, lo
                    int strips, int rows, int chunks, long per_channel) {
   constexpr int NC = 3 * S + 3;
   constexpr int GR = S == 1 ? 3 : 2, GC = S == 1 ? 6 : 5, GLEAD = S == 1 ? 1 : 0;      // window of g: rows yo - GLEAD ..
-  __shared__ float red[4][kUnSums];
+  __shared__ float red[4 * kUnSums];
   const Item it = unit_item(chunks, wq, strips, rows, per_channel);
   float sums[kUnSums];
 #pragma unroll
@@ -236,18 +157,18 @@ unit_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ in, lo
     for (int k = 0; k < 9; ++k) wt[k] = w[c * 9 + k];
     float a[3][NC], gw[GR][GC];
     unsigned pos[3];
-    pos[0] = load_in<NC, RQ, VEC>(src, S * ya - 1, H, W, S * x0, f, a[0]);
-    if (S == 1) pos[1] = load_in<NC, RQ, VEC>(src, ya, H, W, x0, f, a[1]);
+    pos[0] = cdn::load_act<NC, RQ, VEC>(src, S * ya - 1, H, W, S * x0, f, a[0]);
+    if (S == 1) pos[1] = cdn::load_act<NC, RQ, VEC>(src, ya, H, W, x0, f, a[1]);
 #pragma unroll
-    for (int r = 0; r + 1 < GR; ++r) load_row<GC, GLEAD, VEC>(gsrc, ya - GLEAD + r, Ho, Wo, x0, gw[r]);
+    for (int r = 0; r + 1 < GR; ++r) cdn::load_cols<GC, GLEAD, VEC>(gsrc, ya - GLEAD + r, Ho, Wo, x0, gw[r]);
     for (int y = ya; y < yb; ++y) {
       if (S == 1) {
-        pos[2] = load_in<NC, RQ, VEC>(src, y + 1, H, W, x0, f, a[2]);
+        pos[2] = cdn::load_act<NC, RQ, VEC>(src, y + 1, H, W, x0, f, a[2]);
       } else {
-        pos[1] = load_in<NC, RQ, VEC>(src, S * y, H, W, S * x0, f, a[1]);
-        pos[2] = load_in<NC, RQ, VEC>(src, S * y + 1, H, W, S * x0, f, a[2]);
+        pos[1] = cdn::load_act<NC, RQ, VEC>(src, S * y, H, W, S * x0, f, a[1]);
+        pos[2] = cdn::load_act<NC, RQ, VEC>(src, S * y + 1, H, W, S * x0, f, a[2]);
       }
-      load_row<GC, GLEAD, VEC>(gsrc, y - GLEAD + GR - 1, Ho, Wo, x0, gw[GR - 1]);
+      cdn::load_cols<GC, GLEAD, VEC>(gsrc, y - GLEAD + GR - 1, Ho, Wo, x0, gw[GR - 1]);
       // grad_in of the input rows S y + r this output row owns
 #pragma unroll
       for (int r = 0; r < S; ++r) {
@@ -290,7 +211,7 @@ unit_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ in, lo
 #pragma unroll
               for (int e = 0; e < 4; ++e) o[e] = old[e] + o[e];
             }
-            store4<VEC>(drow, W, xs, o);
+            cdn::store4<VEC>(drow, W, xs, o);
           }
         }
       }
@@ -327,36 +248,7 @@ unit_dw_bwd_kernel(const float *__restrict__ g, const float *__restrict__ in, lo
         for (int j = 0; j < GC; ++j) gw[r][j] = gw[r + 1][j];
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int k = 0; k < kUnSums; ++k) {
-    float v = sums[k];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kUnSums) {
-    float s = red[0][threadIdx.x];
-    for (int i = 1; i < nw; ++i) s += red[i][threadIdx.x];
-    part[(long)blockIdx.x * kUnSums + threadIdx.x] = s;
-  }
-}
-
-// grad_w [C][9] and grad_b [C] from the workgroups' partials [C][chunks][10], summed in chunk order
-__global__ void __launch_bounds__(256)
-unit_dw_bwd_reduce_kernel(const float *__restrict__ part, float *__restrict__ gw, float *__restrict__ gb, int C,
-                          int chunks) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * kUnSums) return;
-  const int c = i / kUnSums, k = i % kUnSums;
-  float s = 0.0f;
-  for (int h = 0; h < chunks; ++h) s += part[((long)c * chunks + h) * kUnSums + k];
-  if (k < 9) {
-    if (gw) gw[c * 9 + k] = s;
-  } else if (gb) {
-    gb[c] = s;
-  }
+  cdn::block_sums_store(sums, red, part);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -455,7 +347,6 @@ UnPlan unit_plan(int64_t N, int64_t H, int64_t W, int stride) {
   p.chunks = (int)cdn::ceil_div(p.per_channel, p.threads);
   return p;
 }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -468,15 +359,11 @@ extern "C" int cdn_codenet_unit_dw_forward(const float *in, int64_t in_image_pit
   CDN_REQUIRE(stride == 1 || stride == 2, CDN_ERR_ARG, "stride must be 1 or 2, got %d", stride);
   CDN_REQUIRE(in_image_pitch >= C * H * W, CDN_ERR_ARG, "image pitch of the input below C * H * W");
   CDN_REQUIRE(N * in_image_pitch < (1ll << 31) && N * C * H * W < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
-  cdn::QUpdate qu = cdn::no_qupdate();
-  if (running) {
-    CDN_REQUIRE(x_min && x_max && state && counters, CDN_ERR_ARG, "null QuantAct pointer");
-    CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
-    qu = cdn::make_qupdate(x_min, x_max, state, static_cast<unsigned *>(counters), bits, momentum, 1);
-  }
+  cdn::QUpdate qu;
+  if (int rc = cdn::tracked_qupdate(&qu, x_min, x_max, state, counters, bits, momentum, running)) return rc;
   const UnPlan p = unit_plan(N, H, W, stride);
   CDN_REQUIRE(C * (int64_t)p.chunks < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
-  const bool vec = (W & 3) == 0 && (p.Wo & 3) == 0 && (in_image_pitch & 3) == 0 && aligned16(in) && aligned16(out);
+  const bool vec = (W & 3) == 0 && (p.Wo & 3) == 0 && (in_image_pitch & 3) == 0 && cdn::aligned16(in) && cdn::aligned16(out);
   const unsigned grid = (unsigned)(C * p.chunks);
   const unsigned *ins = static_cast<const unsigned *>(in_state);
   unsigned *copy = running ? static_cast<unsigned *>(state_copy) : nullptr;
@@ -500,7 +387,7 @@ extern "C" int cdn_codenet_unit_dw_forward(const float *in, int64_t in_image_pit
 extern "C" size_t cdn_codenet_unit_dw_backward_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W, int stride) {
   if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
   const UnPlan p = unit_plan(N, H, W, stride);
-  return ((size_t)C * (size_t)p.chunks * kUnSums * sizeof(float) + 255) / 256 * 256;
+  return cdn::round256((size_t)C * (size_t)p.chunks * kUnSums * sizeof(float));
 }
 
 extern "C" int cdn_codenet_unit_dw_backward(const float *g, const float *in, int64_t in_image_pitch, const void *in_state,
@@ -517,11 +404,11 @@ extern "C" int cdn_codenet_unit_dw_backward(const float *g, const float *in, int
               CDN_ERR_UNSUPPORTED, "shape too large");
   const UnPlan p = unit_plan(N, H, W, stride);
   CDN_REQUIRE(C * (int64_t)p.chunks < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
-  CDN_REQUIRE(workspace_bytes >= cdn_codenet_unit_dw_backward_workspace_bytes(N, C, H, W, stride) &&
-                  (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
-              CDN_ERR_WORKSPACE, "workspace too small or not 16-byte aligned");
-  const bool vec = (W & 3) == 0 && (p.Wo & 3) == 0 && (in_image_pitch & 3) == 0 && aligned16(in) && aligned16(g) &&
-                   (!grad_in || ((grad_in_image_pitch & 3) == 0 && aligned16(grad_in)));
+  if (int rc = cdn::check_workspace(workspace, workspace_bytes,
+                                    cdn_codenet_unit_dw_backward_workspace_bytes(N, C, H, W, stride)))
+    return rc;
+  const bool vec = (W & 3) == 0 && (p.Wo & 3) == 0 && (in_image_pitch & 3) == 0 && cdn::aligned16(in) && cdn::aligned16(g) &&
+                   (!grad_in || ((grad_in_image_pitch & 3) == 0 && cdn::aligned16(grad_in)));
   const unsigned grid = (unsigned)(C * p.chunks);
   const unsigned *ins = static_cast<const unsigned *>(in_state);
   float *part = static_cast<float *>(workspace);
@@ -542,9 +429,8 @@ extern "C" int cdn_codenet_unit_dw_backward(const float *g, const float *in, int
 #undef CDN_UBWD
   int rc = cdn::check_launch("codenet unit depthwise backward");
   if (rc || !(grad_w || grad_b)) return rc;
-  unit_dw_bwd_reduce_kernel<<<(unsigned)cdn::ceil_div(C * kUnSums, 256), 256, 0, st>>>(part, grad_w, grad_b, (int)C,
-                                                                                       p.chunks);
-  return cdn::check_launch("codenet unit depthwise backward reduce");
+  return cdn::launch_sums_reduce(part, grad_w, grad_b, (int)C, 1, kUnSums, 1, p.chunks, st,
+                                 "codenet unit depthwise backward reduce");
 }
 
 extern "C" int cdn_codenet_unit_join_forward(const float *y3, const void *act_state, float *out, int slot, const float *x1,
@@ -559,7 +445,7 @@ extern "C" int cdn_codenet_unit_join_forward(const float *y3, const void *act_st
   const int hq = (int)cdn::ceil_div(HW, 4);
   const long items = (long)N * h * hq;
   const unsigned grid = (unsigned)cdn::ceil_div(items, 256);
-  const bool vec = (HW & 3) == 0 && aligned16(y3) && aligned16(out) && (!x1 || (aligned16(x1) && (x1_image_pitch & 3) == 0));
+  const bool vec = (HW & 3) == 0 && cdn::aligned16(y3) && cdn::aligned16(out) && (!x1 || (cdn::aligned16(x1) && (x1_image_pitch & 3) == 0));
   const unsigned *as = static_cast<const unsigned *>(act_state);
   hipStream_t st = cdn::as_stream(stream);
   if (vec)
@@ -582,8 +468,8 @@ extern "C" int cdn_codenet_unit_join_backward(const float *grad_out, const float
   const int hq = (int)cdn::ceil_div(HW, 4);
   const long items = (long)N * h * hq;
   const unsigned grid = (unsigned)cdn::ceil_div(items, 256);
-  const bool vec = (HW & 3) == 0 && aligned16(grad_out) && aligned16(y3) && aligned16(grad_y3) &&
-                   (!grad_x1 || (aligned16(grad_x1) && (grad_x1_image_pitch & 3) == 0));
+  const bool vec = (HW & 3) == 0 && cdn::aligned16(grad_out) && cdn::aligned16(y3) && cdn::aligned16(grad_y3) &&
+                   (!grad_x1 || (cdn::aligned16(grad_x1) && (grad_x1_image_pitch & 3) == 0));
   hipStream_t st = cdn::as_stream(stream);
   if (vec)
     unit_join_bwd_kernel<true><<<grid, 256, 0, st>>>(grad_out, y3, grad_y3, slot, grad_x1, (long)grad_x1_image_pitch,

@@ -23,13 +23,14 @@ autograd functions of codenet_stage.py; this function takes their outputs and re
 floating-point sum has one order, nothing allocates outside the caching allocator, the step is capturable.
 """
 import torch
-import torch.nn as nn
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _native as N_
 from .. import ops
 from . import codenet_stage as CS
+from ._qat_common import (_act_update, _fold_all, _hook_reason, _input_reason, _is_1x1, _is_dw, _placement_reason,
+                          _relu_act_reason, _tracked_act, _weight_prep_structural)
 
 # A/B switch (tools/heads_train_bench.py): the heads of a QAT step on the kernels above (True) or module by module
 # through the framework's autograd (False)
@@ -38,32 +39,12 @@ NATIVE_HEADS = True
 _p = CS._p
 
 
-def _act_update(act, partials, relu):
-    """The QuantAct update from a producer's {min, max} pairs (or, with a frozen range, only scale / zero point):
-    returns the state snapshot the consumers and the backward pass read."""
-    dev = act.x_min.device
-    snap = torch.empty(8, dtype=torch.int32, device=dev)
-    running = bool(act.running_stat)
-    rc = N_.lib().cdn_codenet_head_act_update(
-        _p(act.x_min), _p(act.x_max), _p(act._device_state(dev)), _p(partials) if running else None,
-        partials.shape[0] if running else 0, int(act.activation_bit), float(act.momentum), int(running), int(bool(relu)),
-        _p(snap), torch.cuda.current_stream(dev).cuda_stream)
-    N_.check(rc, "cdn_codenet_head_act_update")
-    return snap
-
-
 def _dw_forward(y1, snap1, w2, b2, act3):
     """r2 = relu(dw3x3(fq1(relu(y1)), w2) + b2) (stored before quantisation) and the snapshot of act3's state."""
     Nb, C, H, W = y1.shape
     r2 = torch.empty_like(y1)
-    if act3.running_stat:
-        snap3 = torch.empty(8, dtype=torch.int32, device=y1.device)
-        upd = ops._update_args(act3, y1.device, False)
-    else:
-        snap3 = _act_update(act3, None, False)
-        upd = (None, None, None, None, int(act3.activation_bit), float(act3.momentum))
-    rc = N_.lib().cdn_codenet_head_dw_forward(_p(y1), _p(snap1), _p(w2), _p(b2), _p(r2), Nb, C, H, W, *upd,
-                                              int(bool(act3.running_stat)), _p(snap3), ops._stream(y1))
+    snap3, upd = _tracked_act(act3, y1.device)
+    rc = N_.lib().cdn_codenet_head_dw_forward(_p(y1), _p(snap1), _p(w2), _p(b2), _p(r2), Nb, C, H, W, *upd, ops._stream(y1))
     N_.check(rc, "cdn_codenet_head_dw_forward")
     return r2, snap3
 
@@ -154,47 +135,23 @@ class CodenetHeadsFunction(Function):
         return tuple(grads)
 
 
-def _is_1x1(conv):
-    return (tuple(conv.kernel_size) == (1, 1) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0)
-            and tuple(conv.dilation) == (1, 1) and conv.groups == 1)
-
-
 def _head_reason(name, mod):
-    from ..portable_quantizer.quant_modules import QuantAct, QuantDepthwiseNode
+    from ..portable_quantizer.quant_modules import QuantDepthwiseNode
     if not isinstance(mod, QuantDepthwiseNode):
         return "head '%s' is a %s, not a QuantDepthwiseNode (the fp32 nn.Sequential heads keep the module path)" % (
             name, type(mod).__name__)
-    for sub_name, m in mod.named_modules():
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None):
-            return "head '%s': a hook on sub-module '%s' must fire, the native path bypasses its __call__" % (
-                name, sub_name or "<the head>")
+    why = _hook_reason(mod, "head '%s'" % name)
+    if why is not None:
+        return why
     for attr in ("quant_act1", "quant_act3"):
-        seq = getattr(mod, attr)
-        if not (isinstance(seq, nn.Sequential) and len(seq) == 2 and isinstance(seq[0], nn.ReLU)
-                and isinstance(seq[1], QuantAct)):
-            return "head '%s': %s is not Sequential(ReLU, QuantAct)" % (name, attr)
-        act = seq[1]
-        if act.percentile:
-            return "head '%s': %s uses percentile statistics (--act-percentile keeps the module path)" % (name, attr)
-        if not CS.native_act_ok(act):
-            return "head '%s': %s is not an asymmetric quantising QuantAct (quant_mode %s, full precision %s)" % (
-                name, attr, act.quant_mode, act.full_precision_flag)
-        if getattr(act, "global_range", False):
-            return "head '%s': %s is in global_range mode" % (name, attr)
+        why = _relu_act_reason(getattr(mod, attr), "head '%s': %s" % (name, attr))
+        if why is not None:
+            return why
     c1, c2, c3 = mod.quant_convbn1.conv, mod.quant_convbn2.conv, mod.quant_conv
     C = c1.out_channels
-    if not (_is_1x1(c1) and _is_1x1(c3) and tuple(c2.kernel_size) == (3, 3) and tuple(c2.stride) == (1, 1)
-            and tuple(c2.padding) == (1, 1) and tuple(c2.dilation) == (1, 1) and c2.groups == c2.in_channels == C
-            and c2.out_channels == C and c3.in_channels == C and getattr(c2, "padding_mode", "zeros") == "zeros"):
+    if not (_is_1x1(c1) and _is_1x1(c3) and _is_dw(c2, 1) and c2.in_channels == C and c3.in_channels == C):
         return "head '%s': not the heads' own geometry (1x1 -> depthwise 3x3, stride 1, zero padding 1 -> 1x1)" % name
     return None
-
-
-def _weight_prep_structural(w, q):
-    """CS.native_weight_prep_ok without the placement of `w`: what the quantiser is, not where the model lives."""
-    k_lo, k_hi, _ = CS.weight_range_ranks(w.numel() // w.shape[0], q.weight_percentile)
-    return (q.per_channel and q.quant_mode == "symmetric" and not q.full_precision_flag and not q.quantize_bias
-            and k_lo <= 4 and k_hi <= 4)
 
 
 def native_reason(heads, x):
@@ -221,24 +178,19 @@ def native_reason(heads, x):
                         "quantising, no bias quantisation)" % name)
     if x is None:
         return None
-    if not torch.is_tensor(x) or not x.is_cuda:
-        return "x is a %s tensor, the kernels run on the GPU" % (x.device.type if torch.is_tensor(x) else type(x).__name__)
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-        return "x must be a contiguous float32 [N, C, H, W] tensor (got %s %s)" % (x.dtype, tuple(x.shape))
-    Nb, Cin, H, W = x.shape
     hidden = next(iter(heads.values())).quant_convbn1.conv.out_channels
-    if Nb > 65535 or Nb * max(Cin, len(heads) * hidden) * H * W >= 2 ** 31:
-        return "x is too large for 32-bit indexing (%s)" % (tuple(x.shape),)
+    why = _input_reason(x, len(heads) * hidden)
+    if why is not None:
+        return why
+    Cin = x.shape[1]
     for name, mod in heads.items():
         if mod.quant_convbn1.conv.in_channels != Cin:
             return "head '%s' expects %d input channels, x has %d" % (name, mod.quant_convbn1.conv.in_channels, Cin)
-        for q, w in ((mod.quant_convbn1, mod.quant_convbn1.conv.weight), (mod.quant_convbn2, mod.quant_convbn2.conv.weight),
-                     (mod.quant_conv, mod.quant_conv.weight)):
-            if not CS.native_weight_prep_ok(w, q):
-                return "head '%s': a weight is not a float32 GPU tensor" % name
-        for act in (mod.quant_act1[1], mod.quant_act3[1]):
-            if act.x_min.device != x.device:
-                return "head '%s': a QuantAct's range buffers are not on x's device" % name
+        why = _placement_reason(x, ((mod.quant_convbn1.conv.weight, mod.quant_convbn1),
+                                    (mod.quant_convbn2.conv.weight, mod.quant_convbn2), (mod.quant_conv.weight, mod.quant_conv)),
+                                (mod.quant_act1[1], mod.quant_act3[1]), "head '%s': " % name)
+        if why is not None:
+            return why
     return None
 
 
@@ -246,18 +198,13 @@ def _prepared_weights(mods):
     """[(W1q, b1, W2q, b2, W3q, b3)] per head: the folds of all heads in one launch and the last convs' quantisers in
     another where the multi-tensor weight prep takes them, else every module's own (native) preparation."""
     cbs = [cb for m in mods for cb in (m.quant_convbn1, m.quant_convbn2)]
+    f = _fold_all(cbs)
     if CS.MULTI_WEIGHT_PREP and len(cbs) <= 8:
-        flat = []
-        for cb in cbs:
-            flat += [cb.conv.weight, cb.conv.bias, cb.bn.weight, cb.bn.bias, cb.bn.running_mean, cb.bn.running_var]
-        f = CS.MultiFoldFakeQuantWeight.apply(tuple((cb.weight_bit, cb.weight_percentile, cb.bn.eps) for cb in cbs), *flat)
         q = CS.MultiFakeQuantWeight.apply(tuple((m.quant_conv.weight_bit, m.quant_conv.weight_percentile) for m in mods),
                                           *[m.quant_conv.weight for m in mods])
-        return [(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3], q[i], m.quant_conv.bias) for i, m in enumerate(mods)]
-    out = []
-    for m in mods:
-        out.append(m.quant_convbn1.folded() + m.quant_convbn2.folded() + (m.quant_conv.quantized_weight(), m.quant_conv.bias))
-    return out
+    else:
+        q = [m.quant_conv.quantized_weight() for m in mods]
+    return [tuple(f[4 * i:4 * i + 4]) + (q[i], m.quant_conv.bias) for i, m in enumerate(mods)]
 
 
 def forward_heads(heads, x, keep=None):

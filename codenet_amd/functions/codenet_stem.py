@@ -27,8 +27,8 @@ from torch.autograd.function import once_differentiable
 from .. import _native as N_
 from .. import ops
 from . import codenet_stage as CS
-from .codenet_heads import _act_update, _weight_prep_structural
-from .codenet_units import _act_reason, _hook_reason
+from ._qat_common import (_act_reason, _hook_reason, _input_reason, _placement_reason, _tracked_act,
+                          _weight_prep_structural)
 
 # A/B switch (tools/stem_train_bench.py): the stem of a QAT step on the kernels above (True) or module by module through the
 # framework's autograd (False)
@@ -42,14 +42,8 @@ def _conv_forward(x, w, b, stride, act):
     Nb, _, H, W = x.shape
     Co = w.shape[0]
     y0 = x.new_empty(Nb, Co, (H - 1) // stride + 1, (W - 1) // stride + 1)
-    if act.running_stat:
-        snap = torch.empty(8, dtype=torch.int32, device=x.device)
-        upd = ops._update_args(act, x.device, False)
-    else:
-        snap = _act_update(act, None, False)
-        upd = (None, None, None, None, int(act.activation_bit), float(act.momentum))
-    rc = N_.lib().cdn_codenet_stem_train_forward(_p(x), _p(w), _p(b), _p(y0), Nb, H, W, Co, stride, *upd,
-                                                 int(bool(act.running_stat)), _p(snap), ops._stream(x))
+    snap, upd = _tracked_act(act, x.device)
+    rc = N_.lib().cdn_codenet_stem_train_forward(_p(x), _p(w), _p(b), _p(y0), Nb, H, W, Co, stride, *upd, ops._stream(x))
     N_.check(rc, "cdn_codenet_stem_train_forward")
     return y0, snap
 
@@ -173,22 +167,10 @@ def native_reason(layer0, x):
         return why
     if x is None:
         return None
-    if torch.is_tensor(x) and x.requires_grad:
-        return "x requires grad: the native stem builds no gradient with respect to the image"
-    if not torch.is_tensor(x) or not x.is_cuda:
-        return "x is a %s tensor, the kernels run on the GPU" % (x.device.type if torch.is_tensor(x) else type(x).__name__)
-    if (x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0 or not x.is_contiguous()
-            or x.data_ptr() % 16):
-        return "x must be a contiguous, 16-byte aligned float32 [N, 3, H, W] tensor (got %s %s)" % (x.dtype, tuple(x.shape))
-    Nb, _, H, W = x.shape
     s = conv.stride[0]
-    if Nb > 65535 or Nb * 3 * H * W >= 2 ** 31 or Nb * 24 * ((H - 1) // s + 1) * ((W - 1) // s + 1) >= 2 ** 31:
-        return "x is too large for 32-bit indexing (%s)" % (tuple(x.shape),)
-    if not CS.native_weight_prep_ok(conv.weight, cb):
-        return "a weight is not a float32 GPU tensor"
-    if act.x_min.device != x.device:
-        return "the QuantAct's range buffers are not on x's device"
-    return None
+    why = _input_reason(x, lambda H, W: max(3 * H * W, 24 * ((H - 1) // s + 1) * ((W - 1) // s + 1)), channels=3,
+                        aligned=True, takes_grad=False)
+    return why or _placement_reason(x, [(conv.weight, cb)], [act])
 
 
 def forward_stem(layer0, x, keep=None):

@@ -35,7 +35,8 @@ from torch.autograd.function import once_differentiable
 from .. import _native as N_
 from .. import ops
 from . import codenet_stage as CS
-from .codenet_heads import _act_update, _is_1x1, _weight_prep_structural
+from ._qat_common import (_act_reason, _act_update, _fold_all, _hook_reason, _input_reason, _is_1x1, _is_dw,
+                          _placement_reason, _relu_act_reason, _tracked_act, _weight_prep_structural)
 
 # A/B switch (tools/units_train_bench.py): the units of a QAT step on the kernels above (True) or module by module through
 # the framework's autograd (False)
@@ -65,14 +66,9 @@ def _dw_forward(in_ptr, in_pitch, in_state, w, b, Nb, C, H, W, stride, act, like
     """The raw depthwise output (stored before quantisation) and the snapshot of the state of the QuantAct behind it."""
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = like.new_empty(Nb, C, Ho, Wo)
-    if act.running_stat:
-        snap = torch.empty(8, dtype=torch.int32, device=like.device)
-        upd = ops._update_args(act, like.device, False)
-    else:
-        snap = _act_update(act, None, False)
-        upd = (None, None, None, None, int(act.activation_bit), float(act.momentum))
+    snap, upd = _tracked_act(act, like.device)
     rc = N_.lib().cdn_codenet_unit_dw_forward(in_ptr, in_pitch, _p(in_state), _p(w), _p(b), _p(y), Nb, C, H, W, stride, *upd,
-                                              int(bool(act.running_stat)), _p(snap), ops._stream(like))
+                                              ops._stream(like))
     N_.check(rc, "cdn_codenet_unit_dw_forward")
     return y, snap
 
@@ -234,35 +230,6 @@ class PointwiseRangeFunction(Function):
         return gx, gw, gb, None
 
 
-def _hook_reason(root, what):
-    for sub_name, m in root.named_modules():
-        if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None):
-            return "%s: a hook on sub-module '%s' must fire, the native path bypasses its __call__" % (
-                what, sub_name or "<the module>")
-    return None
-
-
-def _act_reason(act, what):
-    from ..portable_quantizer.quant_modules import QuantAct
-    if not isinstance(act, QuantAct):
-        return "%s is not a QuantAct" % what
-    if act.percentile:
-        return "%s uses percentile statistics (--act-percentile keeps the module path)" % what
-    if not CS.native_act_ok(act):
-        return "%s is not an asymmetric quantising QuantAct (quant_mode %s, full precision %s)" % (
-            what, act.quant_mode, act.full_precision_flag)
-    if getattr(act, "global_range", False):
-        return "%s is in global_range mode" % what
-    return None
-
-
-def _is_dw(conv, stride):
-    C = conv.in_channels
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (stride, stride) and tuple(conv.padding) == (1, 1)
-            and tuple(conv.dilation) == (1, 1) and conv.groups == C and conv.out_channels == C
-            and getattr(conv, "padding_mode", "zeros") == "zeros")
-
-
 def _node_convbns(node):
     cbs = [node.quant_convbn1, node.quant_convbn2, node.quant_convbn3]
     if node.stride == 2:
@@ -312,17 +279,10 @@ def _is_layer4(mod):
 
 
 def _layer4_reason(layer4):
-    from ..portable_quantizer.quant_modules import QuantAct
-    why = _hook_reason(layer4, "layer4")
+    why = _hook_reason(layer4, "layer4") or _relu_act_reason(layer4[1], "layer4: its second module")
     if why is not None:
         return why
-    cb, post = layer4[0], layer4[1]
-    if not (isinstance(post, nn.Sequential) and len(post) == 2 and isinstance(post[0], nn.ReLU)
-            and isinstance(post[1], QuantAct)):
-        return "layer4: its second module is not Sequential(ReLU, QuantAct)"
-    why = _act_reason(post[1], "layer4: its QuantAct")
-    if why is not None:
-        return why
+    cb = layer4[0]
     if not _is_1x1(cb.conv):
         return "layer4: not a 1x1 convolution"
     if not _weight_prep_structural(cb.conv.weight, cb) or cb.weight_bit > 4:
@@ -364,43 +324,20 @@ def native_reason(node_or_layer, x):
         cin = c.in_channels if nodes[0].stride == 2 else 2 * c.out_channels
     if x is None:
         return None
-    if not torch.is_tensor(x) or not x.is_cuda:
-        return "x is a %s tensor, the kernels run on the GPU" % (x.device.type if torch.is_tensor(x) else type(x).__name__)
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous() or x.data_ptr() % 16:
-        return "x must be a contiguous, 16-byte aligned float32 [N, C, H, W] tensor (got %s %s)" % (x.dtype, tuple(x.shape))
-    Nb, Cx, H, W = x.shape
-    if Cx != cin:
-        return "the first module expects %d input channels, x has %d" % (cin, Cx)
-    widest = max([Cx] + [2 * n.quant_convbn1.conv.out_channels for n in nodes] + ([node_or_layer[0].conv.out_channels]
-                                                                                  if layer4 else []))
-    if Nb > 65535 or Nb * widest * H * W >= 2 ** 31:
-        return "x is too large for 32-bit indexing (%s)" % (tuple(x.shape),)
+    widest = max([node_or_layer[0].conv.out_channels] if layer4 else [2 * n.quant_convbn1.conv.out_channels for n in nodes])
+    why = _input_reason(x, widest, channels=cin, aligned=True)
+    if why is not None:
+        return why
     cbs = [node_or_layer[0]] if layer4 else [cb for n in nodes for cb in _node_convbns(n)]
-    for cb in cbs:
-        if not CS.native_weight_prep_ok(cb.conv.weight, cb):
-            return "a weight is not a float32 GPU tensor"
     acts = [node_or_layer[1][1]] if layer4 else [a for n in nodes for a in (
         [n.quant_act1, n.quant_act2, n.quant_act] + ([n.quant_act4] if n.stride == 2 else []))]
-    for act in acts:
-        if act.x_min.device != x.device:
-            return "a QuantAct's range buffers are not on x's device"
-    return None
+    return _placement_reason(x, [(cb.conv.weight, cb) for cb in cbs], acts)
 
 
 def _prepared_weights(node):
     """(W1q, b1, W2q, b2, W3q, b3[, W4q, b4, W5q, b5]): the folds of the unit in one launch where the multi-tensor weight
     prep takes them, else every module's own (native) preparation."""
-    cbs = _node_convbns(node)
-    if CS.MULTI_WEIGHT_PREP and len(cbs) <= 8:
-        flat = []
-        for cb in cbs:
-            flat += [cb.conv.weight, cb.conv.bias, cb.bn.weight, cb.bn.bias, cb.bn.running_mean, cb.bn.running_var]
-        return tuple(CS.MultiFoldFakeQuantWeight.apply(
-            tuple((cb.weight_bit, cb.weight_percentile, cb.bn.eps) for cb in cbs), *flat))
-    out = ()
-    for cb in cbs:
-        out += tuple(cb.folded())
-    return out
+    return _fold_all(_node_convbns(node))
 
 
 def _unit_meta(node):

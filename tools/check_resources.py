@@ -71,20 +71,20 @@ BUDGET_PREPROC = {"pre_process_kernel": 64, "crop_sum_kernel": 64, "color_aug_ke
 # 46-50 / 37-54 when written), the depthwise backward with its two 3 x 6 windows and ten sums at four (128; 73-104), no
 # scratch
 BUDGET_HEADS_TRAIN = {"head_dw_fwd_kernel": 64, "head_tail_fwd_kernel": 64, "head_dw_bwd_kernelILi": 128,
-                      "head_dw_bwd_reduce_kernel": 64}
+                      "train_sums_reduce_kernel": 64}      # (the reduction of units and stem too: cdn_train.h)
 
 # codenet_units_train.hip (built without the SLP vectoriser, as codenet_heads_train.hip): the same kind of bandwidth-bound
 # register-window kernels -- the depthwise forward (3 x 6 / 3 x 9 window) and the joins at eight waves per SIMD (64 VGPRs;
 # 33-52 / 16-22 when written), the depthwise backward with its input and gradient windows and ten sums at four (128;
 # 64-96), no scratch
 BUDGET_UNITS_TRAIN = {"unit_dw_fwd_kernel": 64, "unit_join_fwd_kernel": 64, "unit_join_bwd_kernel": 64,
-                      "unit_dw_bwd_kernelILi": 128, "unit_dw_bwd_reduce_kernel": 64}
+                      "unit_dw_bwd_kernelILi": 128}
 
 # codenet_stem_train.hip (built without the SLP vectoriser, as codenet_units_train.hip): the forward (27 inputs, one
 # accumulator at a time) and the pool kernels (a 5 x 5 patch) at eight waves per SIMD (64 VGPRs; 57 / 14 / 50 when written);
 # the weight gradient holds 4 x 28 sums beside the 27-value patch and runs at three (168; 160), no scratch
 BUDGET_STEM_TRAIN = {"stem_train_fwd_kernel": 64, "stem_pool_fwd_kernel": 64, "stem_pool_bwd_kernel": 64,
-                     "stem_wgrad_kernel": 168, "stem_wgrad_reduce_kernel": 64}
+                     "stem_wgrad_kernel": 168}
 
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
