@@ -318,7 +318,9 @@ __device__ __forceinline__ void quantact_update_device(const QUpdate &u, float b
     u.x_max[0] = hi;
   }
   const float nlev = (float)((1 << u.bits) - 1);
-  const float range = fmaxf(hi - lo, 1e-10f);          // torch.clamp(min=1e-10)
+  // torch.clamp(min=1e-10), which keeps a NaN (fmaxf would return the bound: a finite scale next to a NaN zero-point)
+  const float width = hi - lo;
+  const float range = width < 1e-10f ? 1e-10f : width;
   // `n / tensor` in torch is Tensor.__rtruediv__ = tensor.reciprocal() * n: two roundings
   const float rcp = __fdiv_rn(1.0f, range);
   const float scale = rcp * nlev;

@@ -215,7 +215,7 @@ relu_fq_up2_kernel(const float *__restrict__ y, float *__restrict__ out, long ro
 }
 
 // The same block WITHOUT the up-sampling (round 4: stages 1-2 of the QAT step read their input at stored resolution,
-// cdn_codenet_dw_up2_*): out[i] = fake_quant(max(y[i], 0)), and its backward grad_y = grad_out where y > 0.
+// cdn_codenet_dw_up2_*): out[i] = fake_quant(max(y[i], 0)), and its backward grad_y = grad_out where !(y <= 0).
 __global__ void __launch_bounds__(256)
 relu_fq_kernel(const float *__restrict__ y, float *__restrict__ out, long n, const unsigned *__restrict__ state) {
   const float scale = reinterpret_cast<const float *>(state)[2];
@@ -232,19 +232,22 @@ relu_fq_kernel(const float *__restrict__ y, float *__restrict__ out, long n, con
   for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     out[i] = fq(y[i]);
 }
+// threshold backward of ReLU as torch computes it (y <= 0 ? 0 : g): the gradient passes at a NaN, so that a diverged
+// step stays loud in the backward pass too (`y > 0 ? g : 0` would return 0 there)
+__device__ __forceinline__ float relu_mask(float y, float g) { return !(y <= 0.0f) ? g : 0.0f; }
 __global__ void __launch_bounds__(256)
 relu_bwd_kernel(const float *__restrict__ g, const float *__restrict__ y, float *__restrict__ gy, long n) {
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const float4 v = reinterpret_cast<const float4 *>(y)[i], a = reinterpret_cast<const float4 *>(g)[i];
-    reinterpret_cast<float4 *>(gy)[i] = make_float4(v.x > 0.f ? a.x : 0.f, v.y > 0.f ? a.y : 0.f, v.z > 0.f ? a.z : 0.f,
-                                                    v.w > 0.f ? a.w : 0.f);
+    reinterpret_cast<float4 *>(gy)[i] = make_float4(relu_mask(v.x, a.x), relu_mask(v.y, a.y), relu_mask(v.z, a.z),
+                                                    relu_mask(v.w, a.w));
   }
   for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    gy[i] = y[i] > 0.f ? g[i] : 0.f;
+    gy[i] = relu_mask(y[i], g[i]);
 }
 
-// backward of that block: grad_y[r][w] = (sum of the 2x2 replicas' gradients) * (y > 0)   (straight-through QuantAct,
+// backward of that block: grad_y[r][w] = (sum of the 2x2 replicas' gradients) where !(y <= 0)   (straight-through QuantAct,
 // quant_utils.py:202-204; threshold backward of ReLU; nearest-upsample backward = sum over the replicas, added in
 // row-major order like at::native::upsample_nearest2d_backward)
 __global__ void __launch_bounds__(256)
@@ -265,8 +268,8 @@ up2_relu_bwd_kernel(const float *__restrict__ g, const float *__restrict__ y, fl
       sa = ((p[0] + p[1]) + p[2L * W]) + p[2L * W + 1];
       if (two) sb = ((p[2] + p[3]) + p[2L * W + 2]) + p[2L * W + 3];
     }
-    gy[r * W + w0] = y[r * W + w0] > 0.0f ? sa : 0.0f;
-    if (two) gy[r * W + w0 + 1] = y[r * W + w0 + 1] > 0.0f ? sb : 0.0f;
+    gy[r * W + w0] = relu_mask(y[r * W + w0], sa);
+    if (two) gy[r * W + w0 + 1] = relu_mask(y[r * W + w0 + 1], sb);
   }
 }
 

@@ -428,16 +428,18 @@ int cdn_quantact_forward(const float *x, float *out, int16_t *codes, int64_t num
  * (lib/models/networks/shufflenetv2_dcn.py:303-308 after quantize_model.py:79-81) as ONE QuantAct call that reads the
  * pre-ReLU tensor y [planes][H][W] once: range tracking on max(y, 0) exactly as cdn_quantact_forward would on the
  * ReLU output (x_min / x_max updated in place when running), out [planes][2H][2W] = the fake-quantised values
- * replicated 2x2.  cdn_up2_relu_backward: grad_y = (sum of the four replicas of grad_out) where y > 0, else 0
- * (straight-through QuantAct, quant_utils.py:202-204). */
+ * replicated 2x2.  cdn_up2_relu_backward: grad_y = 0 where y <= 0, else ((a + b) + c) + d over the four replicas of
+ * grad_out in row-major order (straight-through QuantAct, quant_utils.py:202-204; torch's threshold backward: the
+ * gradient passes where y is NaN).  Only grad_out must be 16-byte aligned. */
 int cdn_quantact_relu_up2_forward(const float *y, float *out, int64_t planes, int64_t H, int64_t W, float *x_min,
                                   float *x_max, void *state, int bits, double momentum, int running, void *stream);
 int cdn_up2_relu_backward(const float *grad_out, const float *y, float *grad_y, int64_t planes, int64_t H, int64_t W,
                           void *stream);
 /* The same block WITHOUT materialising the Upsample (round 4): out [numel] = fake_quant(max(y, 0)) at stored
  * resolution for a consumer that reads its input through the up-sampling (cdn_codenet_dw_up2_*); partials (may be
- * NULL: a range pass over y) as in cdn_quantact_relu_up2_forward_partials.  cdn_relu_backward: grad_y = grad_out where
- * y > 0 (the 2x2 sum of the up-sampling backward has already happened in cdn_codenet_dw_up2_backward). */
+ * NULL: a range pass over y) as in cdn_quantact_relu_up2_forward_partials.  cdn_relu_backward: grad_y = 0 where
+ * y <= 0, else grad_out -- a NaN in y passes the gradient, as torch's ReLU backward does (the 2x2 sum of the
+ * up-sampling backward has already happened in cdn_codenet_dw_up2_backward). */
 int cdn_quantact_relu_forward(const float *y, float *out, int64_t numel, float *x_min, float *x_max, void *state,
                               const float *partials, int64_t n_partials, int bits, double momentum, int running,
                               void *stream);
