@@ -180,6 +180,9 @@ _SIGNATURES = {
     "cdn_codenet_stem_pool_backward": (_i, [_vp] * 4 + [_i64] * 4 + [_vp]),
     "cdn_codenet_stem_backward_workspace_bytes": (ctypes.c_size_t, [_i64] * 3 + [_i]),
     "cdn_codenet_stem_backward": (_i, [_vp] * 5 + [_i64] * 4 + [_i, _vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_bn_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
+    "cdn_codenet_bn_relu_up_forward": (_i, [_vp] * 10 + [_i64] * 4 + [_i, _i, _d, _d, _vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_bn_relu_up_backward": (_i, [_vp] * 10 + [_i64] * 4 + [_i, _i, _vp, ctypes.c_size_t, _vp]),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

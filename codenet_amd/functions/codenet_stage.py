@@ -577,10 +577,19 @@ STORED_RES_STAGES = True
 def forward_stage_blocks(seq, x):
     """``seq(x)`` for a quantised ``deconv_layers`` Sequential; in the QAT step on the GPU the block
     [ReLU, QuantAct] + Upsample(x2, nearest) behind every stage runs as ReluQuantUpsample (one forward and one
-    backward kernel instead of relu / fake-quant / upsample and their three backward kernels)."""
+    backward kernel instead of relu / fake-quant / upsample and their three backward kernels).  For the fp32 model's
+    ``deconv_layers`` -- blocks of [stage, BatchNorm2d, ReLU, Upsample] -- under autograd on the GPU the block behind every
+    stage runs as codenet_bn.BnReluUpsample (codenet_bn.native_reason says why not, when not)."""
     import torch.nn as nn
+    from ..modules.dcn_deform_conv import DeformConvWithOffsetScaleBoundPositive
     from ..portable_quantizer.quant_modules import QuantAct, QuantDeformConvWithOffsetScaleBoundPositive
     mods = list(seq)
+    if mods and isinstance(mods[0], DeformConvWithOffsetScaleBoundPositive):
+        # the fp32 model (main.py): blocks of [stage, BatchNorm2d, ReLU, Upsample] on the kernels of codenet_bn_train.hip
+        from . import codenet_bn
+        if codenet_bn.native_reason(seq, x) is None:
+            return codenet_bn.forward_fp32_blocks(seq, x)
+        return seq(x)
 
     def block_ok(q, post, up):
         return (isinstance(q, QuantDeformConvWithOffsetScaleBoundPositive) and isinstance(post, nn.Sequential)

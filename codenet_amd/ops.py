@@ -400,3 +400,52 @@ def quantact_forward(x, x_min, x_max, state, bits=8, momentum=0.99, running=True
     _toc(rec)
     N_.check(rc, "cdn_quantact_forward")
     return out, codes
+
+
+def _bn_workspace(y, ws):
+    need = N_.lib().cdn_codenet_bn_workspace_bytes(*y.shape)
+    if ws is None:
+        ws = torch.empty(need // 4 + 64, dtype=torch.float32, device=y.device)
+    return ws
+
+
+def bn_relu_up_forward(y, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, up, training,
+                       ws=None):
+    """BatchNorm2d -> ReLU -> Upsample(x up, nearest; up 1 or 2) of y [N,C,H,W] (cdn_codenet_bn_relu_up_forward;
+    shufflenetv2_dcn.py:303-308): (out, mean, var, invstd).  training: batch statistics; the running buffers and the int64
+    batch counter (each may be None) advance IN PLACE.  Otherwise the running statistics are the operands."""
+    _gpu_f32(y, gamma, beta, running_mean, running_var)
+    y = y.contiguous()
+    Nb, C, H, W = y.shape
+    out = y.new_empty(Nb, C, up * H, up * W)
+    stats = y.new_empty(3, C)
+    ws = _bn_workspace(y, ws) if training else None
+    rc = N_.lib().cdn_codenet_bn_relu_up_forward(
+        _p(y), _p(gamma.contiguous()), _p(beta.contiguous()), _p(running_mean), _p(running_var), _p(num_batches_tracked),
+        _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(out), Nb, C, H, W, int(up), int(bool(training)), float(eps),
+        float(momentum if momentum is not None else 0.0), _p(ws), ws.numel() * 4 if ws is not None else 0, _stream(y))
+    N_.check(rc, "cdn_codenet_bn_relu_up_forward")
+    return out, stats[0], stats[1], stats[2]
+
+
+def bn_relu_up_backward(grad_out, y, gamma, beta, mean, invstd, up, training, ws=None, keep_gz=False, keep=None):
+    """Backward of bn_relu_up_forward (cdn_codenet_bn_relu_up_backward): (grad_y, g_z, grad_gamma, grad_beta).  g_z -- the
+    gradient behind the ReLU at stored resolution -- is grad_y's own buffer unless keep_gz (then a tensor of its own).
+    keep (tests): a dict that receives the second pass's per-channel means mb = f32(sum g_z / n), mg = f32(sum g_z xh / n)."""
+    _gpu_f32(grad_out, y, gamma, beta, mean, invstd)
+    y, grad_out = y.contiguous(), grad_out.contiguous()
+    Nb, C, H, W = y.shape
+    if tuple(grad_out.shape) != (Nb, C, up * H, up * W):
+        raise RuntimeError("grad_out must be %s, got %s" % ((Nb, C, up * H, up * W), tuple(grad_out.shape)))
+    gy = torch.empty_like(y)
+    gz = torch.empty_like(y) if keep_gz else gy
+    gg, gb = y.new_empty(C), y.new_empty(C)
+    ws = _bn_workspace(y, ws)
+    rc = N_.lib().cdn_codenet_bn_relu_up_backward(
+        _p(grad_out), _p(y), _p(gamma.contiguous()), _p(beta.contiguous()), _p(mean.contiguous()), _p(invstd.contiguous()),
+        _p(gz), _p(gy), _p(gg), _p(gb), Nb, C, H, W, int(up), int(bool(training)), _p(ws), ws.numel() * 4, _stream(y))
+    N_.check(rc, "cdn_codenet_bn_relu_up_backward")
+    if keep is not None:      # (the workspace's tail: include/codenet_dcn.h)
+        tail = (N_.lib().cdn_codenet_bn_workspace_bytes(Nb, C, H, W) - (C * 8 + 255) // 256 * 256) // 4
+        keep["mb"], keep["mg"] = ws[tail:tail + C].clone(), ws[tail + C:tail + 2 * C].clone()
+    return gy, (gz if keep_gz else None), gg, gb

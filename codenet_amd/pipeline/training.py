@@ -125,7 +125,10 @@ class GraphedTrainStep:
     that tail, from layer0's output -- of a quantised model whose units run on functions/codenet_units.py
     (`is_native_trunk`), and (4) the whole network, ``pipeline.DetectionNet(model)`` -- the stem in front of that trunk,
     from the image -- of a quantised model whose stem runs on functions/codenet_stem.py (`is_native_net`): every kernel of
-    those steps is this library's, every sum has one order.
+    those steps is this library's, every sum has one order; and (5) the fp32 stack of the reference's main.py --
+    ``pipeline.build_hot_path(quantized=False)``: a ``pipeline.DeconvLayers`` (its forward is forward_stage_blocks) of
+    [deform stage, BatchNorm2d, ReLU, Upsample] blocks, BatchNorm in training or eval mode (`is_fp32_stage_stack`; functions/codenet_bn.py, DESIGN.md section 4.3e;
+    tests/test_gpu_bn_block.py shows its replays bit-identical to the eager step).
     tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
     bit-identical from a restored state whatever else the process does in between (a second model built before the capture
     taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
@@ -147,10 +150,11 @@ class GraphedTrainStep:
         (``codenet_amd.losses.CtdetLoss``: its sums are fixed-order slabs of this library's own kernels)."""
 
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
-        if not unvalidated and not self.is_stage_stack(net) and not self.is_native_tail(net) \
-                and not self.is_native_trunk(net) and not self.is_native_net(net):
+        if not unvalidated and not self.is_stage_stack(net) and not self.is_fp32_stage_stack(net) \
+                and not self.is_native_tail(net) and not self.is_native_trunk(net) and not self.is_native_net(net):
             raise NotImplementedError(
-                "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for a "
+                "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for the "
+                "fp32 stack (a pipeline.DeconvLayers of [deform stage, BatchNorm2d, ReLU, Upsample] blocks on functions/codenet_bn), for a "
                 "pipeline.DetectionTail whose heads run natively, for a pipeline.DetectionTrunk whose units run "
                 "natively and for a pipeline.DetectionNet whose stem runs natively only; `net` "
                 "holds other modules, whose PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass "
@@ -185,6 +189,24 @@ class GraphedTrainStep:
         if seq is not net and [m for m in net.children()] != [seq]:
             return False
         return _stage_blocks_ok(seq)
+
+    @staticmethod
+    def is_fp32_stage_stack(net):
+        """True for a pipeline.DeconvLayers -- the container whose forward IS functions/codenet_stage.forward_stage_blocks --
+        of fp32 blocks [DeformConvWithOffsetScaleBoundPositive, BatchNorm2d, ReLU, Upsample(x2, nearest)] that
+        functions/codenet_bn runs natively (native_reason(seq, None) is None: affine BatchNorms that track running statistics
+        with a float momentum, no hooks, NATIVE_FP32_BLOCKS on), BatchNorm in training or eval mode: the stage stack of the
+        reference's main.py.  A bare ``nn.Sequential`` of such blocks, or another container around it, is refused: calling it
+        runs ``Sequential.forward``, the framework's BatchNorm under autograd, which this scope does not cover."""
+        from ..functions.codenet_bn import native_reason
+        from .common import DeconvLayers
+        if not isinstance(net, DeconvLayers) or type(net).forward is not DeconvLayers.forward:
+            return False
+        seq = net.deconv_layers
+        if not isinstance(seq, nn.Sequential) or len(seq) == 0 or [m for m in net.children()] != [seq]:
+            return False
+        with torch.enable_grad():
+            return native_reason(seq, None) is None
 
     @staticmethod
     def is_native_tail(net):

@@ -1194,6 +1194,38 @@ int cdn_codenet_stem_backward(const float *g, const float *y0, const float *img,
                               void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The block behind every deform stage of the fp32 model under autograd -- BatchNorm2d -> ReLU -> Upsample(x2, nearest)
+ * (lib/models/networks/shufflenetv2_dcn.py:303-308) -- forward and backward (codenet_bn_train.hip; DESIGN.md section 4.3e
+ * states the arithmetic, every operation rounded on its own, every sum in float64 in one order, no float atomics).
+ * y [N][C][H][W] float32 NCHW, 16-byte aligned, n = N H W values per channel; up = 1: out / grad_out are [N][C][H][W], up = 2:
+ * [N][C][2H][2W].  mean, var (biased), invstd [C] are outputs of the forward and inputs of the backward.
+ * cdn_codenet_bn_workspace_bytes: the workspace of either call (shufflenetv2_dcn.py:303-308): round_up_256(C * slabs * 16)
+ *   + round_up_256(C * 8), slabs = ceil(n / 4096); 0 for arguments the calls refuse.
+ * cdn_codenet_bn_relu_up_forward (shufflenetv2_dcn.py:303-308): training != 0: mean = f32(S1 / n), var = f32(max(S2 / n -
+ *   (S1 / n)^2, 0)) from the float64 sums S1 = sum y, S2 = sum y^2, invstd = 1 / sqrt(var + eps) (float32, correctly
+ *   rounded); running_mean = (1 - m) running_mean + m mean, running_var = (1 - m) running_var + m f32(var_d n / (n - 1)) and
+ *   *num_batches_tracked += 1 on the device (each may be NULL: not updated; the two running buffers together); n == 1 is
+ *   CDN_ERR_ARG.  training == 0: mean = running_mean, var = running_var, nothing is updated, no workspace is needed.
+ *   Then out = relu(gamma * ((y - mean) * invstd) + beta), a NaN kept.
+ * cdn_codenet_bn_relu_up_backward (shufflenetv2_dcn.py:303-308): g_z [N][C][H][W] = G where z > 0 else 0, z recomputed from
+ *   y as in the forward, G = grad_out (up = 1) or ((g00 + g01) + g10) + g11 of its 2x2 block (up = 2); grad_beta = f32(sum
+ *   g_z), grad_gamma = f32(sum g_z xh), xh = (y - mean) * invstd (either may be NULL); grad_y = ((g_z - mb) - xh mg) *
+ *   (gamma * invstd) with mb = f32(sum g_z / n), mg = f32(sum g_z xh / n) (training != 0) or g_z * (gamma * invstd)
+ *   (training == 0).  grad_y may be g_z itself.  Everything is OVERWRITTEN.
+ * The workspace is the caller's, 16-byte aligned, every word written before it is read (CDN_ERR_WORKSPACE when too small).
+ * Sizes below 2^31 elements per tensor (CDN_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+size_t cdn_codenet_bn_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W);
+int cdn_codenet_bn_relu_up_forward(const float *y, const float *gamma, const float *beta, float *running_mean,
+                                   float *running_var, int64_t *num_batches_tracked, float *mean, float *var, float *invstd,
+                                   float *out, int64_t N, int64_t C, int64_t H, int64_t W, int up, int training, double eps,
+                                   double momentum, void *workspace, size_t workspace_bytes, void *stream);
+int cdn_codenet_bn_relu_up_backward(const float *grad_out, const float *y, const float *gamma, const float *beta,
+                                    const float *mean, const float *invstd, float *g_z, float *grad_y, float *grad_gamma,
+                                    float *grad_beta, int64_t N, int64_t C, int64_t H, int64_t W, int up, int training,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

@@ -86,6 +86,11 @@ BUDGET_UNITS_TRAIN = {"unit_dw_fwd_kernel": 64, "unit_join_fwd_kernel": 64, "uni
 BUDGET_STEM_TRAIN = {"stem_train_fwd_kernel": 64, "stem_pool_fwd_kernel": 64, "stem_pool_bwd_kernel": 64,
                      "stem_wgrad_kernel": 168}
 
+# codenet_bn_train.hip (built without the SLP vectoriser, as codenet_stem_train.hip): streaming kernels bound by HBM, a quad
+# per thread and iteration, that hide latency with occupancy -- eight waves per SIMD (64 VGPRs), no scratch, no spills
+BUDGET_BN_TRAIN = {"bn_stats_kernel": 64, "bn_apply_kernel": 64, "bn_bwd1_kernel": 64, "bn_bwd2_kernel": 64,
+                   "bn_stats_finish_kernel": 64, "bn_bwd_finish_kernel": 64, "bn_eval_stats_kernel": 64}
+
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
     with tempfile.TemporaryDirectory() as tmp:
@@ -124,7 +129,8 @@ def check():
                                ("codenet_loss.hip", (), BUDGET_LOSS), ("codenet_preproc.hip", (), BUDGET_PREPROC),
                                ("codenet_heads_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_TRAIN),
                                ("codenet_units_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_TRAIN),
-                               ("codenet_stem_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_TRAIN)):
+                               ("codenet_stem_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_TRAIN),
+                               ("codenet_bn_train.hip", ("-fno-slp-vectorize",), BUDGET_BN_TRAIN)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -151,7 +157,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))
