@@ -9,80 +9,61 @@ import torch
 import torch.nn as nn
 
 
-class DetectionTail(nn.Module):
-    """Everything of the CoDeNet behind the backbone as one module: the deform stages and the detection heads of `model`
-    (a harness.PoseShuffleNetV2; the modules are SHARED, not copied).  forward(feat) -> [{head: tensor}] from a layer-4
-    feature map, as the model's own forward returns it.  After quantisation every kernel of its training step is this
-    library's (functions/codenet_stage.forward_stage_blocks, functions/codenet_heads.forward_heads)."""
+class _DetectionChain(nn.Module):
+    """The back of a CoDeNet from one of its layers on as one module for the QAT step.  PARTS names what a subclass takes
+    from `model` (a harness.PoseShuffleNetV2) in front of the heads, in registration order; the modules are SHARED, not
+    copied.  forward(x) -> [{head: tensor}], as the model's own forward returns it, always through the training chain
+    functions/codenet_stem.forward_stem -> codenet_units.forward_units x 3 -> forward_layer4 ->
+    codenet_stage.forward_stage_blocks -> codenet_heads.forward_heads, entered at the first part present."""
+    PARTS = ()
 
     def __init__(self, model):
         super().__init__()
         self.heads = dict(model.heads)
-        self.deconv_layers = model.deconv_layers
-        for h in self.heads:
-            setattr(self, h, getattr(model, h))
-
-    def head_modules(self):
-        return {h: getattr(self, h) for h in self.heads}
-
-    def forward(self, feat):
-        from ..functions.codenet_heads import forward_heads
-        from ..functions.codenet_stage import forward_stage_blocks
-        return [forward_heads(self.head_modules(), forward_stage_blocks(self.deconv_layers, feat))]
-
-
-class DetectionTrunk(nn.Module):
-    """Everything of the CoDeNet behind the stem as one module: layers 1-4 of the backbone, the deform stages and the
-    detection heads of `model` (modules SHARED, not copied).  forward(feat0) -> [{head: tensor}] from layer0's output.
-    After quantisation every kernel of its training step is this library's (functions/codenet_units.forward_units /
-    forward_layer4 in front of DetectionTail's chain); the stem stays outside (DetectionNet takes it in)."""
-
-    def __init__(self, model):
-        super().__init__()
-        self.heads = dict(model.heads)
-        for name in ("layer1", "layer2", "layer3", "layer4", "deconv_layers") + tuple(self.heads):
+        for name in self.PARTS + tuple(self.heads):
             setattr(self, name, getattr(model, name))
 
     def head_modules(self):
         return {h: getattr(self, h) for h in self.heads}
 
-    def forward(self, feat0):
+    def forward(self, x):
         from ..functions.codenet_heads import forward_heads
         from ..functions.codenet_stage import forward_stage_blocks
+        from ..functions.codenet_stem import forward_stem
         from ..functions.codenet_units import forward_layer4, forward_units
-        x = feat0
-        for layer in (self.layer1, self.layer2, self.layer3):
-            x = forward_units(layer, x)
-        x = forward_stage_blocks(self.deconv_layers, forward_layer4(self.layer4, x))
-        return [forward_heads(self.head_modules(), x)]
+        if "layer0" in self.PARTS:
+            x = forward_stem(self.layer0, x)
+        if "layer1" in self.PARTS:
+            for layer in (self.layer1, self.layer2, self.layer3):
+                x = forward_units(layer, x)
+        if "layer4" in self.PARTS:
+            x = forward_layer4(self.layer4, x)
+        return [forward_heads(self.head_modules(), forward_stage_blocks(self.deconv_layers, x))]
 
 
-class DetectionNet(nn.Module):
+class DetectionTail(_DetectionChain):
+    """Everything of the CoDeNet behind the backbone as one module: the deform stages and the detection heads of `model`
+    (a harness.PoseShuffleNetV2; the modules are SHARED, not copied).  forward(feat) -> [{head: tensor}] from a layer-4
+    feature map, as the model's own forward returns it.  After quantisation every kernel of its training step is this
+    library's (functions/codenet_stage.forward_stage_blocks, functions/codenet_heads.forward_heads)."""
+    PARTS = ("deconv_layers",)
+
+
+class DetectionTrunk(_DetectionChain):
+    """Everything of the CoDeNet behind the stem as one module: layers 1-4 of the backbone, the deform stages and the
+    detection heads of `model` (modules SHARED, not copied).  forward(feat0) -> [{head: tensor}] from layer0's output.
+    After quantisation every kernel of its training step is this library's (functions/codenet_units.forward_units /
+    forward_layer4 in front of DetectionTail's chain); the stem stays outside (DetectionNet takes it in)."""
+    PARTS = ("layer1", "layer2", "layer3", "layer4", "deconv_layers")
+
+
+class DetectionNet(_DetectionChain):
     """The whole CoDeNet as one module for the QAT step: the stem, layers 1-4 of the backbone, the deform stages and the
     detection heads of `model` (modules SHARED, not copied).  forward(img) -> [{head: tensor}] from the image, always through
     the training chain functions/codenet_stem.forward_stem -> codenet_units.forward_units x 3 -> forward_layer4 ->
     codenet_stage.forward_stage_blocks -> codenet_heads.forward_heads -- never through the inference schedules the model's
     own forward dispatches on.  After quantisation every kernel of its training step is this library's."""
-
-    def __init__(self, model):
-        super().__init__()
-        self.heads = dict(model.heads)
-        for name in ("layer0", "layer1", "layer2", "layer3", "layer4", "deconv_layers") + tuple(self.heads):
-            setattr(self, name, getattr(model, name))
-
-    def head_modules(self):
-        return {h: getattr(self, h) for h in self.heads}
-
-    def forward(self, img):
-        from ..functions.codenet_heads import forward_heads
-        from ..functions.codenet_stage import forward_stage_blocks
-        from ..functions.codenet_stem import forward_stem
-        from ..functions.codenet_units import forward_layer4, forward_units
-        x = forward_stem(self.layer0, img)
-        for layer in (self.layer1, self.layer2, self.layer3):
-            x = forward_units(layer, x)
-        x = forward_stage_blocks(self.deconv_layers, forward_layer4(self.layer4, x))
-        return [forward_heads(self.head_modules(), x)]
+    PARTS = ("layer0",) + DetectionTrunk.PARTS
 
 
 def _stage_blocks_ok(seq):
@@ -98,6 +79,23 @@ def _stage_blocks_ok(seq):
                 and isinstance(up, nn.Upsample)):
             return False
     return True
+
+
+def _outside_scope(net):
+    """None, or the reason why `net`, a DetectionTail / DetectionTrunk / DetectionNet, is outside the validated scope: its
+    stages are not the blocks above, or a part it holds is refused by the gate of the functions/ module that runs it.  (The
+    gates see the caller's grad mode: under no_grad every one refuses, so the predicates built on this are False there.)"""
+    from ..functions import codenet_heads, codenet_stem, codenet_units
+    if not _stage_blocks_ok(net.deconv_layers):
+        return "deconv_layers: not a Sequential of [quantised deform stage, Sequential(ReLU, QuantAct), Upsample] blocks"
+    gated = [("heads", codenet_heads, net.head_modules())]
+    gated += [(name, codenet_units, getattr(net, name)) for name in net.PARTS if name in ("layer1", "layer2", "layer3", "layer4")]
+    gated += [(name, codenet_stem, getattr(net, name)) for name in net.PARTS if name == "layer0"]
+    for name, gate, part in gated:
+        why = gate.native_reason(part, None)
+        if why is not None:
+            return "%s: %s" % (name, why)
+    return None
 
 
 class GraphedTrainStep:
@@ -158,7 +156,8 @@ class GraphedTrainStep:
                 "pipeline.DetectionTail whose heads run natively, for a pipeline.DetectionTrunk whose units run "
                 "natively and for a pipeline.DetectionNet whose stem runs natively only; `net` "
                 "holds other modules, whose PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass "
-                "unvalidated=True to capture it anyway (see the class docstring for what was measured).")
+                "unvalidated=True to capture it anyway (see the class docstring for what was measured)."
+                + (" [%s]" % _outside_scope(net) if isinstance(net, _DetectionChain) else ""))
         self.static = [t.detach().clone() for t in example_inputs]
         for t, src in zip(self.static, example_inputs):
             t.requires_grad_(src.requires_grad)
@@ -184,11 +183,7 @@ class GraphedTrainStep:
         """True for a (container of one) Sequential of [quantised deform stage, Sequential(ReLU, QuantAct), Upsample]
         blocks -- what functions/codenet_stage.forward_stage_blocks runs natively and the bit-level tests cover."""
         seq = getattr(net, "deconv_layers", net)
-        if not isinstance(seq, nn.Sequential) or len(seq) == 0 or len(seq) % 3:
-            return False
-        if seq is not net and [m for m in net.children()] != [seq]:
-            return False
-        return _stage_blocks_ok(seq)
+        return _stage_blocks_ok(seq) and (seq is net or [m for m in net.children()] == [seq])
 
     @staticmethod
     def is_fp32_stage_stack(net):
@@ -214,20 +209,14 @@ class GraphedTrainStep:
         functions/codenet_heads.forward_heads runs natively (native_reason(heads, None) is None: quantised heads with
         the default QuantAct settings, no hooks, NATIVE_HEADS on) -- stages, heads and, with losses.CtdetLoss, the
         criterion are then one chain of this library's kernels."""
-        from ..functions.codenet_heads import native_reason
-        return (isinstance(net, DetectionTail) and _stage_blocks_ok(net.deconv_layers)
-                and native_reason(net.head_modules(), None) is None)
+        return isinstance(net, DetectionTail) and _outside_scope(net) is None
 
     @staticmethod
     def is_native_trunk(net):
         """True for a pipeline.DetectionTrunk whose stages and heads are what `is_native_tail` accepts and whose layers 1-3
         and layer4 functions/codenet_units runs natively (native_reason(layer, None) is None: QuantBaseNode units with the
         default QuantAct settings, no hooks, NATIVE_UNITS on)."""
-        from ..functions.codenet_heads import native_reason as heads_reason
-        from ..functions.codenet_units import native_reason as units_reason
-        return (isinstance(net, DetectionTrunk) and _stage_blocks_ok(net.deconv_layers)
-                and heads_reason(net.head_modules(), None) is None
-                and all(units_reason(getattr(net, name), None) is None for name in ("layer1", "layer2", "layer3", "layer4")))
+        return isinstance(net, DetectionTrunk) and _outside_scope(net) is None
 
     @staticmethod
     def is_native_net(net):
@@ -235,12 +224,7 @@ class GraphedTrainStep:
         stem functions/codenet_stem runs natively (native_reason(layer0, None) is None: the quantised 3 -> 24 stem with the
         default QuantAct settings, no hooks, NATIVE_STEM on) -- image -> loss -> optimizer is then one chain of this
         library's kernels."""
-        from ..functions.codenet_heads import native_reason as heads_reason
-        from ..functions.codenet_stem import native_reason as stem_reason
-        from ..functions.codenet_units import native_reason as units_reason
-        return (isinstance(net, DetectionNet) and _stage_blocks_ok(net.deconv_layers)
-                and heads_reason(net.head_modules(), None) is None and stem_reason(net.layer0, None) is None
-                and all(units_reason(getattr(net, name), None) is None for name in ("layer1", "layer2", "layer3", "layer4")))
+        return isinstance(net, DetectionNet) and _outside_scope(net) is None
 
     def set_lr(self, value, group=None):
         """Write a new learning rate where the captured step reads it: the param group's lr must be a device TENSOR

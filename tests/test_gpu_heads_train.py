@@ -16,25 +16,22 @@ Smallest shapes at which the kernels can go wrong: N = 2, C = 64, planes 12 x 20
 16 x 16 and 9 x 10 (width no multiple of 4: the scalar-load path), heads 20 / 2 / 2 and one case with 80 classes.
 """
 import copy
-import types
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from oracle import quant as Q
+from tests import qat_support
 
 pytestmark = pytest.mark.gpu
 
 HEADS = ("hm", "wh", "reg")
-U = 2.0 ** -24
 CASES = [(12, 20, 20), (16, 16, 20), (9, 10, 20), (16, 16, 80)]      # (H, W, classes of hm)
 
 
-def _model(classes=20, **kw):
-    from codenet_amd import harness
-    return harness.create_model(heads={"hm": classes, "wh": 2, "reg": 2}, quantize=True, **kw)
+_model, _codes, _fq32, _bound, _within = (qat_support.model, qat_support.codes, qat_support.fq32, qat_support.bound,
+                                          qat_support.within)
 
 
 def _heads_of(model):
@@ -42,17 +39,6 @@ def _heads_of(model):
 
 
 # ---- 1. exact arithmetic -------------------------------------------------------------------------------------------------
-
-def _codes(g, rows, cols, nonzero):
-    """Integer codes in [-7, 7], `nonzero` non-zero entries per row, one of them +-7."""
-    w = torch.zeros(rows, cols)
-    for r in range(rows):
-        idx = torch.randperm(cols, generator=g)[:nonzero]
-        v = torch.randint(1, 8, (nonzero,), generator=g).float() * (torch.randint(0, 2, (nonzero,), generator=g) * 2 - 1).float()
-        v[0] = 7.0 if v[0] > 0 else -7.0
-        w[r, idx] = v
-    return w
-
 
 def exact_heads(classes, seed=5):
     """The heads of a quantised model with weights / BatchNorms / ranges on which every float32 sum is exact."""
@@ -182,24 +168,6 @@ def test_exact_arithmetic_forward_and_backward_equal_the_cpu_module_path(H, W, c
 
 
 # ---- 2. running ranges, real arithmetic on the kernels' own intermediates ------------------------------------------------
-
-def _fq32(v, x_min, x_max):
-    """Fake-quantisation in float32, the reference's expression order (every operation rounds the same on both sides)."""
-    scale, zp = Q.act_params(x_min, x_max)
-    return Q.act_dequant(Q.act_codes(v, scale, zp), scale, zp)
-
-
-def _bound(n, S):
-    return 1.01 * (n + 2) * U * S
-
-
-def _within(got, ref, n, S, what):
-    err = (got.double().cpu() - ref).abs()
-    tol = _bound(n, S)
-    worst = float((err - tol).max())
-    print("%-28s max err %.3e, smallest slack %.3e (bound up to %.3e)" % (what, float(err.max()), -worst, float(tol.max())))
-    assert worst <= 0, what
-
 
 def _project(got, ref, what, rel=3e-6):
     """The project's bound for the existing pointwise / weight-gradient kernels (tests/test_train_step.py)."""
@@ -347,88 +315,24 @@ def test_own_intermediates_through_the_oracle_quantiser_and_float64(H, W, classe
 
 # ---- 3. reproducibility and capture -------------------------------------------------------------------------------------
 
-def _default_opt():
-    return types.SimpleNamespace(mse_loss=False, reg_loss="l1", dense_wh=False, norm_wh=False, cat_spec_wh=False,
-                                 num_stacks=1, hm_weight=1.0, wh_weight=0.1, off_weight=1.0, reg_offset=True)
-
-
-def _objects(N, M, H, W, seed):
-    rng = np.random.default_rng(seed)
-    c = rng.uniform([1, 1], [W - 2, H - 2], (N, M, 2))
-    s = rng.uniform(0.8, 12.0, (N, M, 2))
-    boxes = np.concatenate([c - s / 2, c + s / 2], 2)
-    boxes[..., [0, 2]] = np.clip(boxes[..., [0, 2]], 0, W - 1)
-    boxes[..., [1, 3]] = np.clip(boxes[..., [1, 3]], 0, H - 1)
-    return (torch.from_numpy(boxes.astype(np.float32)).cuda(), torch.from_numpy(rng.integers(0, 20, (N, M))).cuda(),
-            torch.from_numpy(rng.integers(1, M + 1, N)).cuda())
-
-
 def _tail():
     from codenet_amd import pipeline
-    net = pipeline.DetectionTail(_model()).cuda().train()
-    for m in net.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.eval()
-    return net
-
-
-def _tail_state(net, opt):
-    ts = list(net.parameters()) + list(net.buffers())
-    for st in opt.state.values():
-        ts += [v for v in st.values() if torch.is_tensor(v)]
-    ts += [m._state for m in net.modules() if torch.is_tensor(getattr(m, "_state", None))]
-    return ts
+    return qat_support.train_net(pipeline.DetectionTail)
 
 
 def _tail_setup():
-    from codenet_amd.losses import CtdetLoss, ctdet_targets
-    N, M, R = 2, 8, 32
-    crit = CtdetLoss(_default_opt())
-    batch = ctdet_targets(*_objects(N, M, R, R, 3), 20, R, R, M)
-
-    def loss_fn(net, feat):
-        out = net(feat)
-        assert crit.native_reason(out, batch) is None
-        return crit(out, batch)[0]
-
-    g = torch.Generator().manual_seed(2)
-    feats = [(torch.randn(N, 1024, 4, 4, generator=g).abs_() * 1.66).cuda() for _ in range(5)]
-    return loss_fn, feats
+    return qat_support.step_setup(lambda g, N, R: torch.randn(N, 1024, 4, 4, generator=g).abs_() * 1.66, 5)
 
 
 def test_detection_tail_captured_step_replays_the_eager_step_bit_for_bit():
     from codenet_amd import pipeline
     from codenet_amd.functions import codenet_heads as CH
     loss_fn, feats = _tail_setup()
-
-    def build():
-        net = _tail()
-        return net, torch.optim.Adam(net.parameters(), lr=torch.tensor(1.25e-4, device="cuda"), capturable=True)
-
-    net_e, opt_e = build()
-    net_g, opt_g = build()
+    eager, (net_g, opt_g) = [qat_support.with_capturable_adam(_tail()) for _ in range(2)]
     assert pipeline.GraphedTrainStep.is_native_tail(net_g) and not pipeline.GraphedTrainStep.is_stage_stack(net_g)
     assert CH.native_reason(net_g.head_modules(), torch.empty(2, 64, 32, 32, device="cuda")) is None
-    step = pipeline.GraphedTrainStep(net_g, opt_g, loss_fn, (feats[0],), warmup=3)      # (no `unvalidated`)
-    for _ in range(3):
-        opt_e.zero_grad(set_to_none=True)
-        loss_fn(net_e, feats[0]).backward()
-        opt_e.step()
-    for x in feats[1:]:      # four steps
-        opt_e.zero_grad(set_to_none=True)
-        le = loss_fn(net_e, x)
-        le.backward()
-        opt_e.step()
-        lg = step(x)
-        assert torch.equal(le.detach(), lg.detach())
-    torch.cuda.synchronize()
-    assert le.detach().item() == le.detach().item() and le.detach().item() > 0
-    for (n1, p1), (n2, p2) in zip(net_e.named_parameters(), net_g.named_parameters()):
-        assert torch.equal(p1, p2), n1
-        if n1.split(".")[0] in HEADS:      # every head took part in the loss
-            assert p1.grad is not None and float(p1.grad.abs().sum()) > 0, n1
-    for u, v in zip(_tail_state(net_e, opt_e), _tail_state(net_g, opt_g)):      # ranges, Adam state, device words
-        assert torch.equal(u, v)
+    # four steps; every head took part in the loss
+    qat_support.check_captured_step(eager, (net_g, opt_g), loss_fn, feats, lambda n: n.split(".")[0] in HEADS)
     # with the switch off the same net runs the framework's backward: not accepted as validated
     CH.NATIVE_HEADS = False
     try:
@@ -441,23 +345,7 @@ def test_detection_tail_captured_step_replays_the_eager_step_bit_for_bit():
 
 def test_detection_tail_two_identical_runs_end_bit_identical():
     loss_fn, feats = _tail_setup()
-
-    def run():
-        net = _tail()
-        opt = torch.optim.Adam(net.parameters(), lr=1.25e-4)
-        losses = []
-        for x in feats[:4]:
-            opt.zero_grad(set_to_none=True)
-            loss = loss_fn(net, x)
-            loss.backward()
-            opt.step()
-            losses.append(loss.item())
-        return losses, [t.detach().clone() for t in _tail_state(net, opt)]
-
-    l1, s1 = run()
-    l2, s2 = run()
-    assert l1 == l2
-    assert len(s1) == len(s2) and all(torch.equal(u, v) for u, v in zip(s1, s2))
+    qat_support.check_two_identical_runs(_tail, loss_fn, feats[:4])
 
 
 # ---- 4. gating ---------------------------------------------------------------------------------------------------------------

@@ -20,25 +20,20 @@ eight chunks of the weight gradient, two positions per thread in the pooled case
 (8192 and 32768 positions: the weight gradient's full eight positions per thread, as at the QAT shape).
 """
 import copy
-import types
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from oracle import quant as Q
+from tests import qat_support
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 # (maxpool, H, W)
 CASES = [(False, 36, 44), (False, 17, 22), (False, 64, 64), (True, 36, 44), (True, 17, 22), (True, 64, 64)]
 
-
-def _model(**kw):
-    from codenet_amd import harness
-    return harness.create_model(heads={"hm": 20, "wh": 2, "reg": 2}, quantize=True, **kw)
+_model, _fq32, _within, _SLACK = qat_support.model, qat_support.fq32, qat_support.within, qat_support.SLACK
 
 
 def _parts(layer0):
@@ -170,24 +165,6 @@ def test_exact_arithmetic_forward_and_backward_equal_the_cpu_module_path(maxpool
 
 # ---- 2. running ranges, real arithmetic on the kernels' own intermediates ------------------------------------------------
 
-def _fq32(v, x_min, x_max):
-    """Fake-quantisation in float32, the reference's expression order (every operation rounds the same on both sides)."""
-    scale, zp = Q.act_params(x_min, x_max)
-    return Q.act_dequant(Q.act_codes(v, scale, zp), scale, zp)
-
-
-_SLACK = []
-
-
-def _within(got, ref, n, S, what):
-    err = (got.detach().double().cpu() - ref).abs()
-    tol = 1.01 * (n + 2) * U * S
-    worst = float((err - tol).max())
-    _SLACK.append((-worst, what))
-    print("%-44s max err %.3e, smallest slack %.3e (bound up to %.3e)" % (what, float(err.max()), -worst, float(tol.max())))
-    assert worst <= 0, what
-
-
 def _conv_ref(x, w, b, g, stride):
     """float64 forward / parameter gradients of the stem's convolution from float32 operands, and the sums of magnitudes."""
     res = []
@@ -263,53 +240,13 @@ def test_own_intermediates_ranges_through_the_oracle_and_every_kernel_against_fl
 
 # ---- 3. reproducibility and capture -------------------------------------------------------------------------------------
 
-def _default_opt():
-    return types.SimpleNamespace(mse_loss=False, reg_loss="l1", dense_wh=False, norm_wh=False, cat_spec_wh=False,
-                                 num_stacks=1, hm_weight=1.0, wh_weight=0.1, off_weight=1.0, reg_offset=True)
-
-
-def _objects(N, M, H, W, seed):
-    rng = np.random.default_rng(seed)
-    c = rng.uniform([1, 1], [W - 2, H - 2], (N, M, 2))
-    s = rng.uniform(0.8, 12.0, (N, M, 2))
-    boxes = np.concatenate([c - s / 2, c + s / 2], 2)
-    boxes[..., [0, 2]] = np.clip(boxes[..., [0, 2]], 0, W - 1)
-    boxes[..., [1, 3]] = np.clip(boxes[..., [1, 3]], 0, H - 1)
-    return (torch.from_numpy(boxes.astype(np.float32)).cuda(), torch.from_numpy(rng.integers(0, 20, (N, M))).cuda(),
-            torch.from_numpy(rng.integers(1, M + 1, N)).cuda())
-
-
 def _net(maxpool=False):
     from codenet_amd import pipeline
-    net = pipeline.DetectionNet(_model(maxpool=maxpool)).cuda().train()
-    for m in net.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.eval()
-    return net
-
-
-def _state(net, opt):
-    ts = list(net.parameters()) + list(net.buffers())
-    for st in opt.state.values():
-        ts += [v for v in st.values() if torch.is_tensor(v)]
-    ts += [m._state for m in net.modules() if torch.is_tensor(getattr(m, "_state", None))]
-    return ts
+    return qat_support.train_net(pipeline.DetectionNet, maxpool=maxpool)
 
 
 def _net_setup():
-    from codenet_amd.losses import CtdetLoss, ctdet_targets
-    N, M, R = 2, 8, 32
-    crit = CtdetLoss(_default_opt())
-    batch = ctdet_targets(*_objects(N, M, R, R, 3), 20, R, R, M)
-
-    def loss_fn(net, img):
-        out = net(img)
-        assert crit.native_reason(out, batch) is None
-        return crit(out, batch)[0]
-
-    g = torch.Generator().manual_seed(2)
-    imgs = [(torch.randint(0, 256, (N, 3, 4 * R, 4 * R), generator=g).float() / 64 - 2).cuda() for _ in range(4)]
-    return loss_fn, imgs
+    return qat_support.step_setup(lambda g, N, R: torch.randint(0, 256, (N, 3, 4 * R, 4 * R), generator=g).float() / 64 - 2, 4)
 
 
 @pytest.mark.parametrize("maxpool", [False, True])
@@ -317,36 +254,12 @@ def test_detection_net_captured_step_replays_the_eager_step_bit_for_bit(maxpool)
     from codenet_amd import pipeline
     from codenet_amd.functions import codenet_stem as ST
     loss_fn, imgs = _net_setup()
-
-    def build():
-        net = _net(maxpool)
-        return net, torch.optim.Adam(net.parameters(), lr=torch.tensor(1.25e-4, device="cuda"), capturable=True)
-
-    net_e, opt_e = build()
-    net_g, opt_g = build()
+    eager, (net_g, opt_g) = [qat_support.with_capturable_adam(_net(maxpool)) for _ in range(2)]
     G = pipeline.GraphedTrainStep
     assert G.is_native_net(net_g) and not G.is_native_trunk(net_g) and not G.is_native_tail(net_g) and not G.is_stage_stack(net_g)
     assert ST.native_reason(net_g.layer0, imgs[0]) is None
-    step = G(net_g, opt_g, loss_fn, (imgs[0],), warmup=3)      # (no `unvalidated`)
-    for _ in range(3):
-        opt_e.zero_grad(set_to_none=True)
-        loss_fn(net_e, imgs[0]).backward()
-        opt_e.step()
-    for x in imgs[1:]:      # three steps
-        opt_e.zero_grad(set_to_none=True)
-        le = loss_fn(net_e, x)
-        le.backward()
-        opt_e.step()
-        lg = step(x)
-        assert torch.equal(le.detach(), lg.detach())
-    torch.cuda.synchronize()
-    assert le.detach().item() == le.detach().item() and le.detach().item() > 0
-    for (n1, p1), (n2, p2) in zip(net_e.named_parameters(), net_g.named_parameters()):
-        assert torch.equal(p1, p2), n1
-    w0 = dict(net_e.named_parameters())["layer0.0.conv.weight"]
-    assert w0.grad is not None and float(w0.grad.abs().sum()) > 0      # the stem took part in the loss
-    for u, v in zip(_state(net_e, opt_e), _state(net_g, opt_g)):      # ranges, Adam state, device words
-        assert torch.equal(u, v)
+    # three steps; the stem took part in the loss
+    qat_support.check_captured_step(eager, (net_g, opt_g), loss_fn, imgs, lambda n: n == "layer0.0.conv.weight")
     if maxpool:
         return
     # the bare model stays outside the validated scope; so does the net with the stem's switch off
@@ -365,23 +278,7 @@ def test_detection_net_captured_step_replays_the_eager_step_bit_for_bit(maxpool)
 
 def test_detection_net_two_identical_runs_end_bit_identical():
     loss_fn, imgs = _net_setup()
-
-    def run():
-        net = _net()
-        opt = torch.optim.Adam(net.parameters(), lr=1.25e-4)
-        losses = []
-        for x in imgs[:3]:
-            opt.zero_grad(set_to_none=True)
-            loss = loss_fn(net, x)
-            loss.backward()
-            opt.step()
-            losses.append(loss.item())
-        return losses, [t.detach().clone() for t in _state(net, opt)]
-
-    l1, s1 = run()
-    l2, s2 = run()
-    assert l1 == l2
-    assert len(s1) == len(s2) and all(torch.equal(u, v) for u, v in zip(s1, s2))
+    qat_support.check_two_identical_runs(_net, loss_fn, imgs[:3])
 
 
 def test_detection_net_is_the_bare_model_in_train_mode_head_by_head():

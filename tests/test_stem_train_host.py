@@ -145,6 +145,27 @@ def test_forward_stem_is_the_module_path_on_cpu_tensors():
                 assert float(a[1][1].x_max) > 0      # the QuantAct's range moved in place
 
 
+def test_the_three_wrappers_share_the_models_modules_in_one_registration_order():
+    from codenet_amd import pipeline
+    model = _model()
+    heads = list(model.heads)
+    assert heads == ["hm", "wh", "reg"]
+    layers = ["layer0", "layer1", "layer2", "layer3", "layer4"]
+    classes = {pipeline.DetectionTail: [], pipeline.DetectionTrunk: layers[1:], pipeline.DetectionNet: layers}
+    for cls, front in classes.items():
+        w = cls(model)
+        names = front + ["deconv_layers"] + heads      # layers ascending, the stages, the heads in model.heads order
+        assert [n for n, _ in w.named_children()] == names, cls.__name__
+        assert all(getattr(w, n) is getattr(model, n) for n in names)
+        own = dict(model.named_parameters())
+        params = list(w.named_parameters())
+        assert params and all(p is own[n] for n, p in params), cls.__name__      # the model's own objects, under its names
+        assert [n for n, _ in params] == [n for n in own if n.split(".")[0] in names]      # (and so an optimizer's order)
+        assert list(w.state_dict()) == [k for k in model.state_dict() if k.split(".")[0] in names]
+        assert type(w.heads) is dict and w.heads == dict(model.heads) and list(w.head_modules()) == heads
+        assert not any(issubclass(cls, other) for other in classes if other is not cls)
+
+
 def test_is_native_net_accepts_the_whole_net_and_rejects_everything_else():
     from codenet_amd import pipeline
     model = _model()

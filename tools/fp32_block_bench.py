@@ -24,13 +24,12 @@ out: kilobytes):
 --step: the captured training step (pipeline.GraphedTrainStep, fused Adam) of the same stack, native and module path (the
 latter needs unvalidated=True).  GPU only."""
 import json
-import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+import qat_bench
 from codenet_amd import _native as N_
 from codenet_amd import ops, pipeline
 from codenet_amd.functions import codenet_bn as BN
@@ -68,13 +67,7 @@ def _median_ms(fn, reps=20, warm=3, calls=10):
         for _ in range(calls):
             fn()
     graph.replay()
-    ev = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        graph.replay()
-        b.record()
-        ev.append((a, b))
+    ev = [qat_bench.timed(graph.replay) for _ in range(reps)]
     torch.cuda.synchronize()
     return float(np.median([a.elapsed_time(b) for a, b in ev])) / calls
 
@@ -130,33 +123,10 @@ def main(regions=24, warm=3, batch=32, res=512):
             p.grad = None
         net(x).backward(gy)
 
-    def timed(native):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step(native)
-        b.record()
-        return a, b
-
-    try:
-        for _ in range(warm):
-            step(True), step(False)
-        torch.cuda.synchronize()
-        ev = {True: [], False: []}
-        for _ in range(regions):
-            ev[True].append(timed(True))
-            ev[False].append(timed(False))
-        torch.cuda.synchronize()
-    finally:
-        BN.NATIVE_FP32_BLOCKS = True
-    ms = {k: np.array([a.elapsed_time(b) for a, b in v]) for k, v in ev.items()}
-    nat, mod = float(np.median(ms[True])), float(np.median(ms[False]))
+    nat_ms, mod_ms = qat_bench.interleaved_ab(step, lambda: setattr(BN, "NATIVE_FP32_BLOCKS", True), regions, warm)
     b_nat, b_mod = algorithmic_bytes(net, x)
     res_ = {"shape": "x=[%d,1024,%d,%d] fp32 deconv_layers, BatchNorm in training mode" % (batch, res // 32, res // 32),
-            "regions": regions, "native_fwd_bwd_ms": round(nat, 4), "module_fwd_bwd_ms": round(mod, 4),
-            "module_over_native": round(mod / nat, 3),
-            "native_min_ms": round(float(ms[True].min()), 4), "native_max_ms": round(float(ms[True].max()), 4),
-            "module_min_ms": round(float(ms[False].min()), 4), "module_max_ms": round(float(ms[False].max()), 4),
-            "pairs_native_below_module": int(np.sum(ms[True] < ms[False])),
+            **qat_bench.report(nat_ms, mod_ms, ratio_digits=3), "pairs_native_below_module": int(np.sum(nat_ms < mod_ms)),
             "block_bytes_native_mb": round(b_nat / 1e6, 1), "block_bytes_module_mb": round(b_mod / 1e6, 1),
             "kernels_stage2_tensor": kernel_rates(batch, 64, res // 8, res // 8)}
     print(json.dumps(res_))
@@ -165,7 +135,6 @@ def main(regions=24, warm=3, batch=32, res=512):
 
 def captured_step(batch=32, res=512, steps=20):
     """--step: the captured training step of the stack with fused Adam, native and module path, wall clock over replays."""
-    import time
     x = pipeline.make_input(batch, res, device="cuda")
     out = {}
     try:
@@ -179,14 +148,7 @@ def captured_step(batch=32, res=512, steps=20):
                 return y.square().reshape(-1, 64).sum(1).sum() / y.numel()
 
             step = pipeline.GraphedTrainStep(net, opt, loss_fn, (x,), warmup=3, unvalidated=not native)
-            for _ in range(3):
-                step.graph.replay()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                step.graph.replay()
-            torch.cuda.synchronize()
-            out["native_ms_per_step" if native else "module_ms_per_step"] = round((time.perf_counter() - t0) / steps * 1e3, 3)
+            out["native_ms_per_step" if native else "module_ms_per_step"] = round(qat_bench.replay_s(step, steps) * 1e3, 3)
     finally:
         BN.NATIVE_FP32_BLOCKS = True
     out["config"] = "fp32 deconv_layers %dx%d, batch %d, BatchNorm in training mode, fused Adam, one HIP graph" % (res, res, batch)

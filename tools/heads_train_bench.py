@@ -6,17 +6,15 @@ x = [32, 64, 128, 128].  HIP events, one process, after warm-up:
       timed in INTERLEAVED regions (a, b, a, b, ...) so that clock and temperature drift hit both alike.
 
 Both include the weight preparation (fold + fake-quantisation, native either way) and the gradients of x and of every
-parameter.  Prints one JSON line: the medians, the ratio, whether (a) < (b) held in every pair, and the native path's
+parameter.  Prints one JSON line: the medians, min / max, the ratio, whether (a) < (b) held in every pair, and the native path's
 algorithmic HBM bytes -- every pass over a [N, 64, H, W] tensor it has to make, plus the thin y3 / grad_y3 -- divided by
 its time.  --step: the captured step of the whole detection tail instead (see tail_step).  GPU only."""
 import json
-import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
+import qat_bench
 from codenet_amd import harness
 from codenet_amd.functions import codenet_heads as CH
 
@@ -57,32 +55,9 @@ def main(regions=40, warm=3, N=32, R=128):
         out = CH.forward_heads(heads, x)
         torch.autograd.backward([out[h] for h in heads], gys)
 
-    def timed(native):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step(native)
-        b.record()
-        return a, b
-
-    try:
-        for _ in range(warm):
-            step(True), step(False)
-        torch.cuda.synchronize()
-        ev = {True: [], False: []}
-        for _ in range(regions):
-            ev[True].append(timed(True))
-            ev[False].append(timed(False))
-        torch.cuda.synchronize()
-    finally:
-        CH.NATIVE_HEADS = True
-    ms = {k: np.array([a.elapsed_time(b) for a, b in v]) for k, v in ev.items()}
-    nat, mod = float(np.median(ms[True])), float(np.median(ms[False]))
-    moved = algorithmic_bytes(N, 64, R * R, list(model.heads.values()))
-    res = {"shape": "x=[%d,64,%d,%d] heads=%s" % (N, R, R, dict(model.heads)), "regions": regions,
-           "native_fwd_bwd_ms": round(nat, 4), "module_fwd_bwd_ms": round(mod, 4), "module_over_native": round(mod / nat, 2),
-           "native_below_module_in_every_pair": bool(np.all(ms[True] < ms[False])),
-           "native_max_ms": round(float(ms[True].max()), 4), "module_min_ms": round(float(ms[False].min()), 4),
-           "native_bytes_moved_mb": round(moved / 1e6, 1), "native_gb_per_s": round(moved / nat / 1e6, 1)}
+    ms = qat_bench.interleaved_ab(step, lambda: setattr(CH, "NATIVE_HEADS", True), regions, warm)
+    res = {"shape": "x=[%d,64,%d,%d] heads=%s" % (N, R, R, dict(model.heads)),
+           **qat_bench.report(*ms, algorithmic_bytes(N, 64, R * R, list(model.heads.values())))}
     print(json.dumps(res))
     return res
 
@@ -91,39 +66,11 @@ def tail_step(batch=32, res=512, steps=20):
     """--step: the captured QAT step of the detection tail -- deform stages, heads, losses.CtdetLoss, fused Adam -- as
     pipeline.GraphedTrainStep accepts it without `unvalidated`, timed over `steps` replays (wall clock around the
     replays, as tools/train_step_bench.py times cfg5's step over the stages alone)."""
-    import time
-    import types
     from codenet_amd import pipeline
-    from codenet_amd.losses import CtdetLoss, ctdet_targets
-    net = pipeline.DetectionTail(harness.create_model(quantize=True)).cuda().train()
-    for m in net.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.eval()
-    R, M = res // 4, 50
-    rng = np.random.default_rng(1)
-    c = rng.uniform([1, 1], [R - 2, R - 2], (batch, M, 2))
-    s = rng.uniform(0.8, 40.0, (batch, M, 2))
-    boxes = torch.from_numpy(np.clip(np.concatenate([c - s / 2, c + s / 2], 2), 0, R - 1).astype(np.float32)).cuda()
-    targets = ctdet_targets(boxes, torch.from_numpy(rng.integers(0, 20, (batch, M))).cuda(),
-                            torch.from_numpy(rng.integers(M // 2, M + 1, batch)).cuda(), 20, R, R, M)
-    crit = CtdetLoss(types.SimpleNamespace(mse_loss=False, reg_loss="l1", dense_wh=False, norm_wh=False, cat_spec_wh=False,
-                                           num_stacks=1, hm_weight=1.0, wh_weight=0.1, off_weight=1.0, reg_offset=True))
+    net = qat_bench.bn_eval(pipeline.DetectionTail(harness.create_model(quantize=True)).cuda().train())
     feat = pipeline.make_input(batch, res, device="cuda").requires_grad_(True)      # (as cfg5: the backbone would need it)
-    opt = torch.optim.Adam(net.parameters(), lr=torch.tensor(1.25e-4, device="cuda"), capturable=True, fused=True)
-    step = pipeline.GraphedTrainStep(net, opt, lambda n, f: crit(n(f), targets)[0], (feat,), warmup=3)
-    for _ in range(3):
-        step.graph.replay()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        step.graph.replay()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / steps
-    res_ = {"config": "CoDeNet1x %dx%d W4A8 QAT step over deconv_layers + heads + CtdetLoss, batch %d, one HIP graph" % (
-        res, res, batch), "ms_per_step": round(dt * 1e3, 3), "images_per_s": round(batch / dt, 1),
-        "loss": float(step.loss.detach())}
-    print(json.dumps(res_))
-    return res_
+    return qat_bench.captured_step(net, feat, "CoDeNet1x %dx%d W4A8 QAT step over deconv_layers + heads + CtdetLoss, batch %d, "
+                                   "one HIP graph" % (res, res, batch), res, steps)
 
 
 if __name__ == "__main__":

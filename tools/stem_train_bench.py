@@ -22,13 +22,11 @@ O = N 24 Hp Wp 4 (the pooled output, Y / 4):
 --maxpool: the "S2 + MaxPool" stem.  --step: the captured step of pipeline.DetectionNet (stem, layers 1-4, stages, heads,
 CtdetLoss, fused Adam) instead.  GPU only."""
 import json
-import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
 import torch
 
+import qat_bench
 from codenet_amd import harness
 from codenet_amd.functions import codenet_stem as ST
 
@@ -44,10 +42,7 @@ def algorithmic_bytes(layer0, N, H, W):
 
 
 def main(maxpool=False, regions=30, warm=3, N=32, R=512):
-    model = harness.create_model(quantize=True, maxpool=maxpool).cuda().train()
-    for m in model.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.eval()
+    model = qat_bench.bn_eval(harness.create_model(quantize=True, maxpool=maxpool).cuda().train())
     layer0 = model.layer0
     params = list(layer0.parameters())
     g = torch.Generator().manual_seed(1)
@@ -63,33 +58,9 @@ def main(maxpool=False, regions=30, warm=3, N=32, R=512):
             p.grad = None
         ST.forward_stem(layer0, x).backward(gy)
 
-    def timed(native):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step(native)
-        b.record()
-        return a, b
-
-    try:
-        for _ in range(warm):
-            step(True), step(False)
-        torch.cuda.synchronize()
-        ev = {True: [], False: []}
-        for _ in range(regions):
-            ev[True].append(timed(True))
-            ev[False].append(timed(False))
-        torch.cuda.synchronize()
-    finally:
-        ST.NATIVE_STEM = True
-    ms = {k: np.array([a.elapsed_time(b) for a, b in v]) for k, v in ev.items()}
-    nat, mod = float(np.median(ms[True])), float(np.median(ms[False]))
-    moved = algorithmic_bytes(layer0, N, R, R)
+    ms = qat_bench.interleaved_ab(step, lambda: setattr(ST, "NATIVE_STEM", True), regions, warm)
     res = {"shape": "x=[%d,3,%d,%d] layer0%s" % (N, R, R, " (stride 2 + MaxPool)" if maxpool else " (stride 4)"),
-           "regions": regions, "native_fwd_bwd_ms": round(nat, 4), "module_fwd_bwd_ms": round(mod, 4),
-           "module_over_native": round(mod / nat, 2), "native_below_module_in_every_pair": bool(np.all(ms[True] < ms[False])),
-           "native_min_ms": round(float(ms[True].min()), 4), "native_max_ms": round(float(ms[True].max()), 4),
-           "module_min_ms": round(float(ms[False].min()), 4), "module_max_ms": round(float(ms[False].max()), 4),
-           "native_bytes_moved_mb": round(moved / 1e6, 1), "native_gb_per_s": round(moved / nat / 1e6, 1)}
+           **qat_bench.report(*ms, algorithmic_bytes(layer0, N, R, R))}
     print(json.dumps(res))
     return res
 
@@ -98,40 +69,13 @@ def net_step(maxpool=False, batch=32, res=512, steps=20):
     """--step: the captured QAT step of the whole network -- stem, layers 1-4, deform stages, heads, losses.CtdetLoss, fused
     Adam -- as pipeline.GraphedTrainStep accepts it without `unvalidated`, timed over `steps` replays (wall clock around the
     replays, as tools/units_train_bench.py --step times the trunk's)."""
-    import time
-    import types
     from codenet_amd import pipeline
-    from codenet_amd.losses import CtdetLoss, ctdet_targets
-    net = pipeline.DetectionNet(harness.create_model(quantize=True, maxpool=maxpool)).cuda().train()
-    for m in net.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            m.eval()
-    R, M = res // 4, 50
-    rng = np.random.default_rng(1)
-    c = rng.uniform([1, 1], [R - 2, R - 2], (batch, M, 2))
-    s = rng.uniform(0.8, 40.0, (batch, M, 2))
-    boxes = torch.from_numpy(np.clip(np.concatenate([c - s / 2, c + s / 2], 2), 0, R - 1).astype(np.float32)).cuda()
-    targets = ctdet_targets(boxes, torch.from_numpy(rng.integers(0, 20, (batch, M))).cuda(),
-                            torch.from_numpy(rng.integers(M // 2, M + 1, batch)).cuda(), 20, R, R, M)
-    crit = CtdetLoss(types.SimpleNamespace(mse_loss=False, reg_loss="l1", dense_wh=False, norm_wh=False, cat_spec_wh=False,
-                                           num_stacks=1, hm_weight=1.0, wh_weight=0.1, off_weight=1.0, reg_offset=True))
+    net = qat_bench.bn_eval(pipeline.DetectionNet(harness.create_model(quantize=True, maxpool=maxpool)).cuda().train())
     g = torch.Generator().manual_seed(1)
     img = (torch.randint(0, 256, (batch, 3, res, res), generator=g).float() / 64 - 2).cuda()
-    opt = torch.optim.Adam(net.parameters(), lr=torch.tensor(1.25e-4, device="cuda"), capturable=True, fused=True)
-    step = pipeline.GraphedTrainStep(net, opt, lambda n, f: crit(n(f), targets)[0], (img,), warmup=3)
-    for _ in range(3):
-        step.graph.replay()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        step.graph.replay()
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / steps
-    res_ = {"config": "CoDeNet1x %dx%d W4A8 QAT step over the whole network%s (layer0-4 + deconv_layers + heads + CtdetLoss), "
-                      "batch %d, one HIP graph" % (res, res, " (S2 + MaxPool stem)" if maxpool else "", batch),
-            "ms_per_step": round(dt * 1e3, 3), "images_per_s": round(batch / dt, 1), "loss": float(step.loss.detach())}
-    print(json.dumps(res_))
-    return res_
+    return qat_bench.captured_step(net, img, "CoDeNet1x %dx%d W4A8 QAT step over the whole network%s (layer0-4 + deconv_layers + "
+                                   "heads + CtdetLoss), batch %d, one HIP graph" % (
+                                       res, res, " (S2 + MaxPool stem)" if maxpool else "", batch), res, steps)
 
 
 if __name__ == "__main__":
