@@ -183,6 +183,14 @@ _SIGNATURES = {
     "cdn_codenet_bn_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
     "cdn_codenet_bn_relu_up_forward": (_i, [_vp] * 10 + [_i64] * 4 + [_i, _i, _d, _d, _vp, ctypes.c_size_t, _vp]),
     "cdn_codenet_bn_relu_up_backward": (_i, [_vp] * 10 + [_i64] * 4 + [_i, _i, _vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_head_fp32_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
+    "cdn_codenet_head_fp32_bn_stats": (_i, [_vp] * 7 + [_i64] * 4 + [_i, _d, _d, _vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_head_fp32_dw_forward": (_i, [_vp] * 7 + [_i64] * 4 + [_vp]),
+    "cdn_codenet_head_fp32_tail_forward": (_i, [_vp] * 8 + [_i64] * 5 + [_vp]),
+    "cdn_codenet_head_fp32_tail_backward": (_i, [_vp] * 14 + [_i64] * 5 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_head_fp32_bn_backward1": (_i, [_vp] * 11 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_head_fp32_dw_backward": (_i, [_vp] * 7 + [_i] + [_vp] * 12 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_head_fp32_bn_backward2": (_i, [_vp] * 8 + [_i64] * 5 + [_i, _vp]),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

@@ -209,9 +209,14 @@ def _prepared_weights(mods):
 
 def forward_heads(heads, x, keep=None):
     """{name: head(x)} for an ordered mapping name -> head module.  In the QAT step on the GPU (native_reason(heads, x)
-    is None) all heads run as one CodenetHeadsFunction; otherwise exactly ``{h: mod(x)}``.  keep (tests): a dict that
-    receives per head the native path's y1 and r2."""
+    is None) all heads run as one CodenetHeadsFunction; the fp32 heads of main.py under autograd on the GPU
+    (codenet_heads_fp32.native_reason(heads, x) is None) as one CodenetHeadsFp32Function; otherwise exactly
+    ``{h: mod(x)}``.  keep (tests): a dict that receives per head the native path's y1 and r2 (fp32: y1, y2 and both
+    BatchNorms' numbers)."""
     if native_reason(heads, x) is not None:
+        from . import codenet_heads_fp32
+        if codenet_heads_fp32.native_reason(heads, x) is None:
+            return codenet_heads_fp32.forward_fp32_heads(heads, x, keep)
         return {h: mod(x) for h, mod in heads.items()}
     names = list(heads)
     mods = [heads[h] for h in names]

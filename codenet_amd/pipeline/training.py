@@ -98,6 +98,20 @@ def _outside_scope(net):
     return None
 
 
+def _fp32_tail_outside_scope(net):
+    """None, or the reason why `net`, a DetectionTail, is not the fp32 tail GraphedTrainStep.is_fp32_tail accepts."""
+    from ..functions import codenet_bn, codenet_heads_fp32
+    seq = net.deconv_layers
+    if not isinstance(seq, nn.Sequential) or len(seq) == 0:
+        return "deconv_layers: not a Sequential of [deform stage, BatchNorm2d, ReLU, Upsample] blocks"
+    with torch.enable_grad():      # (a property of the modules, as is_fp32_stage_stack)
+        why = codenet_bn.native_reason(seq, None)
+        if why is not None:
+            return "deconv_layers: %s" % why
+        why = codenet_heads_fp32.native_reason(net.head_modules(), None)
+    return "heads: %s" % why if why is not None else None
+
+
 class GraphedTrainStep:
     """One training step -- forward, loss, backward, optimizer -- over static input buffers as ONE HIP graph.
 
@@ -126,7 +140,11 @@ class GraphedTrainStep:
     those steps is this library's, every sum has one order; and (5) the fp32 stack of the reference's main.py --
     ``pipeline.build_hot_path(quantized=False)``: a ``pipeline.DeconvLayers`` (its forward is forward_stage_blocks) of
     [deform stage, BatchNorm2d, ReLU, Upsample] blocks, BatchNorm in training or eval mode (`is_fp32_stage_stack`; functions/codenet_bn.py, DESIGN.md section 4.3e;
-    tests/test_gpu_bn_block.py shows its replays bit-identical to the eager step).
+    tests/test_gpu_bn_block.py shows its replays bit-identical to the eager step); and (6) the fp32 tail,
+    ``pipeline.DetectionTail(model)`` of an fp32 model: those blocks in front of the fp32 detection heads [Conv2d 1x1,
+    BatchNorm2d, ReLU, depthwise Conv2d 3x3, BatchNorm2d, ReLU, Conv2d 1x1] on functions/codenet_heads_fp32.py, every
+    BatchNorm in training or eval mode (`is_fp32_tail`; tests/test_gpu_heads_fp32.py shows its
+    replays with the native criterion bit-identical to the eager steps).
     tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
     bit-identical from a restored state whatever else the process does in between (a second model built before the capture
     taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
@@ -149,7 +167,8 @@ class GraphedTrainStep:
 
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
         if not unvalidated and not self.is_stage_stack(net) and not self.is_fp32_stage_stack(net) \
-                and not self.is_native_tail(net) and not self.is_native_trunk(net) and not self.is_native_net(net):
+                and not self.is_native_tail(net) and not self.is_native_trunk(net) and not self.is_native_net(net) \
+                and not self.is_fp32_tail(net):
             raise NotImplementedError(
                 "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for the "
                 "fp32 stack (a pipeline.DeconvLayers of [deform stage, BatchNorm2d, ReLU, Upsample] blocks on functions/codenet_bn), for a "
@@ -157,7 +176,10 @@ class GraphedTrainStep:
                 "natively and for a pipeline.DetectionNet whose stem runs natively only; `net` "
                 "holds other modules, whose PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass "
                 "unvalidated=True to capture it anyway (see the class docstring for what was measured)."
-                + (" [%s]" % _outside_scope(net) if isinstance(net, _DetectionChain) else ""))
+                + (" [%s]" % _outside_scope(net) if isinstance(net, _DetectionChain) else "")
+                + " Also validated: the fp32 tail, a pipeline.DetectionTail of an fp32 model whose [deform stage, BatchNorm2d, "
+                "ReLU, Upsample] blocks run on functions/codenet_bn and whose heads run on functions/codenet_heads_fp32"
+                + (" [%s]" % _fp32_tail_outside_scope(net) if isinstance(net, DetectionTail) else "") + ".")
         self.static = [t.detach().clone() for t in example_inputs]
         for t, src in zip(self.static, example_inputs):
             t.requires_grad_(src.requires_grad)
@@ -202,6 +224,16 @@ class GraphedTrainStep:
             return False
         with torch.enable_grad():
             return native_reason(seq, None) is None
+
+    @staticmethod
+    def is_fp32_tail(net):
+        """True for a pipeline.DetectionTail of an fp32 model: ``deconv_layers`` a Sequential of the blocks
+        `is_fp32_stage_stack` describes (functions/codenet_bn.native_reason(seq, None) is None) and heads that
+        functions/codenet_heads_fp32 runs natively (native_reason(heads, None) is None: the seven-module Sequential of
+        shufflenetv2_dcn.py:246-258 with affine BatchNorms that track running statistics with a float momentum, one hidden
+        width, no hooks, NATIVE_FP32_HEADS on), every BatchNorm in training or eval mode.  A property of the modules: the
+        caller's grad mode does not change the answer.  `is_native_tail` stays False for it."""
+        return isinstance(net, DetectionTail) and _fp32_tail_outside_scope(net) is None
 
     @staticmethod
     def is_native_tail(net):

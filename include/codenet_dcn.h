@@ -1226,6 +1226,73 @@ int cdn_codenet_bn_relu_up_backward(const float *grad_out, const float *y, const
                                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The fp32 detection heads under autograd (lib/models/networks/shufflenetv2_dcn.py:246-258): Conv2d 1x1 -> BatchNorm2d ->
+ * ReLU -> depthwise Conv2d 3x3 (zero padding 1) -> BatchNorm2d -> ReLU -> Conv2d 1x1 + bias; codenet_heads_fp32_train.hip;
+ * DESIGN.md section 4.3f states the arithmetic: every float32 operation rounded on its own, every sum in float64 in one
+ * order, no float atomics.  The two dense convolutions of a head and their gradients are cdn_codenet_pointwise_forward /
+ * cdn_codenet_pointwise_wgrad, a wide head's stored a2 is cdn_codenet_bn_relu_up_forward with up = 1.  All tensors float32
+ * NCHW [N][C][H][W] unless stated, n = N H W values per channel; mean, var (biased), invstd, mb, mg, gamma, beta are [C].
+ * Never stored: a1 = relu(bn1(y1)), grad_y2, the unmasked grad_a1 and, for Co <= 4, a2 = relu(bn2(y2)) and grad_a2.
+ * cdn_codenet_head_fp32_workspace_bytes: the workspace of every call below: round_up_256(8 * max(C * slabs * 10,
+ *   N * C * chunks * 11)), slabs = ceil(n / 4096), chunks = ceil(ceil(W / 4) * ceil(H / 8) / 256); 0 for arguments the calls
+ *   refuse.
+ * cdn_codenet_head_fp32_bn_stats: the statistics pass of cdn_codenet_bn_relu_up_forward alone (the same kernels): mean, var,
+ *   invstd of y and, training != 0, the update of running_mean / running_var / *num_batches_tracked (each may be NULL; n == 1
+ *   is CDN_ERR_ARG); training == 0: mean = running_mean, var = running_var, nothing is updated, no workspace is needed.
+ * cdn_codenet_head_fp32_dw_forward: y2 = dw3x3(a1, w2 [C][9]) with a1 = relu(gamma1 * ((y1 - mean1) * invstd1) + beta1)
+ *   formed on load, 0 outside the plane; y2 = ((0 + w[0] a[0]) + w[1] a[1]) + .. + w[8] a[8], taps row-major.
+ * cdn_codenet_head_fp32_tail_forward: y3 [N][Co][H][W] = (sum_c w3[o][c] a2[c]) + b3[o] (b3 may be NULL), c ascending from
+ *   zero, a2 = relu(bn2(y2)) formed on load; 1 <= Co <= 4 (Co > 4: CDN_ERR_UNSUPPORTED; Co < 1: CDN_ERR_ARG).
+ * cdn_codenet_head_fp32_tail_backward (1 <= Co <= 4): from grad_y3 [N][Co][H][W] and y2: grad_a2 = w3[0][c] g[0] (+ w3[o][c]
+ *   g[o], o ascending), g_z2 = grad_a2 where z2 > 0 else 0 (stored); grad_beta2 = f32(T1), grad_gamma2 = f32(T2), mb2 =
+ *   f32(T1 / n), mg2 = f32(T2 / n) with T1 = sum g_z2, T2 = sum g_z2 xh2; grad_w3 [Co][C] = f32(sum g[o] a2) and grad_b3 [Co] =
+ *   f32(sum g[o]) (either may be NULL).
+ * cdn_codenet_head_fp32_bn_backward1: the first backward pass of cdn_codenet_bn_relu_up_backward (up = 1) alone: g_z = grad_a
+ *   where z > 0 else 0 (g_z must not be grad_a), grad_gamma, grad_beta, mb, mg as above.
+ * cdn_codenet_head_fp32_dw_backward: grad_y2 = ((g_z2 - mb2) - xh2 mg2) * (gamma2 * invstd2) (training2 != 0) or g_z2 * (gamma2
+ *   * invstd2) (training2 == 0: mb2 / mg2 not read) formed on load, 0 outside the plane; grad_a1[q] = sum_t w2[c][t] grad_y2[q -
+ *   t]; g_z1 = grad_a1 where z1 > 0 else 0 (stored); grad_w2 [C][9] = f32(sum_p grad_y2[p] a1[p + t]); grad_beta1, grad_gamma1,
+ *   mb1, mg1 from T1 = sum g_z1, T2 = sum g_z1 xh1.
+ * cdn_codenet_head_fp32_bn_backward2: grad_y = ((g_z - mb) - xh mg) * (gamma * invstd) (training != 0) or g_z * (gamma *
+ *   invstd), written to grad_y + n * grad_y_image_pitch + c * H * W: a channel slice of a wider [N][heads * C][H][W] buffer.
+ * Every call takes a stream, allocates nothing, launches no memset node and is capturable.  The workspace is the caller's,
+ * 16-byte aligned, every word written before it is read (CDN_ERR_WORKSPACE when too small).  16-byte loads where W % 4 == 0
+ * and the pointers (and the pitch) are 16-byte aligned, scalar loads otherwise: the same terms in the same order.  Sizes below
+ * 2^31 elements per tensor (CDN_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call.  Everything
+ * written is OVERWRITTEN.
+ * ---------------------------------------------------------------------------------------- */
+size_t cdn_codenet_head_fp32_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W);
+int cdn_codenet_head_fp32_bn_stats(const float *y, float *running_mean, float *running_var, int64_t *num_batches_tracked,
+                                   float *mean, float *var, float *invstd, int64_t N, int64_t C, int64_t H, int64_t W,
+                                   int training, double eps, double momentum, void *workspace, size_t workspace_bytes,
+                                   void *stream);
+int cdn_codenet_head_fp32_dw_forward(const float *y1, const float *mean1, const float *invstd1, const float *gamma1,
+                                     const float *beta1, const float *w2, float *y2, int64_t N, int64_t C, int64_t H,
+                                     int64_t W, void *stream);
+int cdn_codenet_head_fp32_tail_forward(const float *y2, const float *mean2, const float *invstd2, const float *gamma2,
+                                       const float *beta2, const float *w3, const float *b3, float *y3, int64_t N, int64_t C,
+                                       int64_t Co, int64_t H, int64_t W, void *stream);
+int cdn_codenet_head_fp32_tail_backward(const float *grad_y3, const float *y2, const float *mean2, const float *invstd2,
+                                        const float *gamma2, const float *beta2, const float *w3, float *g_z2,
+                                        float *grad_gamma2, float *grad_beta2, float *mb2, float *mg2, float *grad_w3,
+                                        float *grad_b3, int64_t N, int64_t C, int64_t Co, int64_t H, int64_t W,
+                                        void *workspace, size_t workspace_bytes, void *stream);
+int cdn_codenet_head_fp32_bn_backward1(const float *grad_a, const float *y, const float *mean, const float *invstd,
+                                       const float *gamma, const float *beta, float *g_z, float *grad_gamma, float *grad_beta,
+                                       float *mb, float *mg, int64_t N, int64_t C, int64_t H, int64_t W, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+int cdn_codenet_head_fp32_dw_backward(const float *g_z2, const float *y2, const float *mean2, const float *invstd2,
+                                      const float *gamma2, const float *mb2, const float *mg2, int training2, const float *y1,
+                                      const float *mean1, const float *invstd1, const float *gamma1, const float *beta1,
+                                      const float *w2, float *g_z1, float *grad_w2, float *grad_gamma1, float *grad_beta1,
+                                      float *mb1, float *mg1, int64_t N, int64_t C, int64_t H, int64_t W, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+int cdn_codenet_head_fp32_bn_backward2(const float *g_z, const float *y, const float *mean, const float *invstd,
+                                       const float *gamma, const float *mb, const float *mg, float *grad_y,
+                                       int64_t grad_y_image_pitch, int64_t N, int64_t C, int64_t H, int64_t W, int training,
+                                       void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

@@ -91,6 +91,15 @@ BUDGET_STEM_TRAIN = {"stem_train_fwd_kernel": 64, "stem_pool_fwd_kernel": 64, "s
 BUDGET_BN_TRAIN = {"bn_stats_kernel": 64, "bn_apply_kernel": 64, "bn_bwd1_kernel": 64, "bn_bwd2_kernel": 64,
                    "bn_stats_finish_kernel": 64, "bn_bwd_finish_kernel": 64, "bn_eval_stats_kernel": 64}
 
+# codenet_heads_fp32_train.hip (built without the SLP vectoriser, as codenet_bn_train.hip, whose kernels it shares through
+# cdn_bn.h): the register-window kernels of the QAT heads with BatchNorm + ReLU formed on load -- the depthwise forward and the
+# narrow tail at eight waves per SIMD (64 VGPRs), the depthwise backward with its two 3 x 6 windows, the xh rows and eleven
+# float64 sums at four (128); the (channel, slab) kernel of the narrow tail's backward and the pitched second pass at eight;
+# no scratch
+BUDGET_HEADS_FP32_TRAIN = {"head32_dw_fwd_kernel": 64, "head32_tail_fwd_kernel": 64, "head32_dw_bwd_kernelILb": 128,
+                           "head32_tail_bwd_kernelILi": 64, "head32_bn_bwd2_kernel": 64, "head32_tail_bwd_finish_kernel": 64,
+                           "head32_dw_bwd_finish_kernel": 64, "bn_stats_kernel": 64, "bn_bwd1_kernelILi1": 64,
+                           "bn_stats_finish_kernel": 64, "bn_bwd_finish_kernel": 64, "bn_eval_stats_kernel": 64}
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
     with tempfile.TemporaryDirectory() as tmp:
@@ -130,7 +139,8 @@ def check():
                                ("codenet_heads_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_TRAIN),
                                ("codenet_units_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_TRAIN),
                                ("codenet_stem_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_TRAIN),
-                               ("codenet_bn_train.hip", ("-fno-slp-vectorize",), BUDGET_BN_TRAIN)):
+                               ("codenet_bn_train.hip", ("-fno-slp-vectorize",), BUDGET_BN_TRAIN),
+                               ("codenet_heads_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_FP32_TRAIN)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -157,7 +167,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN) + list(BUDGET_HEADS_FP32_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))
