@@ -191,6 +191,14 @@ _SIGNATURES = {
     "cdn_codenet_head_fp32_bn_backward1": (_i, [_vp] * 11 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
     "cdn_codenet_head_fp32_dw_backward": (_i, [_vp] * 7 + [_i] + [_vp] * 12 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
     "cdn_codenet_head_fp32_bn_backward2": (_i, [_vp] * 8 + [_i64] * 5 + [_i, _vp]),
+    "cdn_codenet_unit_fp32_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
+    "cdn_codenet_unit_fp32_dw_forward": (_i, [_vp, _i64] + [_vp] * 6 + [_i64] * 4 + [_i, _vp]),
+    "cdn_codenet_unit_fp32_bn_forward": (_i, [_vp] * 6 + [_i64] * 4 + [_vp]),
+    "cdn_codenet_unit_fp32_join_forward": (_i, [_vp] * 6 + [_i, _vp, _i64] + [_i64] * 4 + [_vp]),
+    "cdn_codenet_unit_fp32_join_backward": (_i, [_vp] * 11 + [_i, _vp, _i64] + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_unit_fp32_bn_backward_sums": (_i, [_vp] * 8 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_unit_fp32_dw_backward": (_i, [_vp] * 7 + [_i, _vp, _i64] + [_vp] * 5 + [_vp, _i64, _i] + [_vp] * 5
+                                          + [_i64] * 4 + [_i, _vp, ctypes.c_size_t, _vp]),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

@@ -347,9 +347,13 @@ def _unit_meta(node):
 
 def forward_units(layer, x, keep=None):
     """``layer(x)`` for a layer of the backbone (a Sequential of QuantBaseNode, or one node).  In the QAT step on the GPU
-    (native_reason(layer, x) is None) every unit runs as one CodenetUnitFunction; otherwise exactly ``layer(x)``.
+    (native_reason(layer, x) is None) every unit runs as one CodenetUnitFunction; an fp32 layer of BaseNode units that
+    codenet_units_fp32.native_reason accepts runs as one CodenetUnitFp32Function per unit; otherwise exactly ``layer(x)``.
     keep (tests): a dict that receives {unit index: the native path's own intermediates}."""
     if native_reason(layer, x) is not None:
+        from . import codenet_units_fp32 as U32
+        if U32.native_reason(layer, x) is None:
+            return U32.forward_fp32_units(layer, x, keep)
         return layer(x)
     nodes = list(layer) if isinstance(layer, nn.Sequential) else [layer]
     for i, node in enumerate(nodes):
@@ -362,8 +366,13 @@ def forward_units(layer, x, keep=None):
 
 def forward_layer4(layer4, x):
     """``layer4(x)`` for the quantised layer4 (QuantBnConv2d 1x1 -> ReLU -> QuantAct): in the QAT step on the GPU the
-    pointwise kernel (with the {min, max} pairs of its output) and CS.ReluQuant; otherwise exactly ``layer4(x)``."""
+    pointwise kernel (with the {min, max} pairs of its output) and CS.ReluQuant; the fp32 layer4 that
+    codenet_units_fp32.native_reason accepts on the pointwise kernel and the fused BatchNorm + ReLU; otherwise exactly
+    ``layer4(x)``."""
     if not _is_layer4(layer4) or native_reason(layer4, x) is not None:
+        from . import codenet_units_fp32 as U32
+        if U32.native_reason(layer4, x) is None:
+            return U32.forward_fp32_layer4(layer4, x)
         return layer4(x)
     cb, act = layer4[0], layer4[1][1]
     w, b = cb.folded()

@@ -112,6 +112,18 @@ def _fp32_tail_outside_scope(net):
     return "heads: %s" % why if why is not None else None
 
 
+def _fp32_trunk_outside_scope(net):
+    """None, or the reason why `net`, a DetectionTrunk, is not the fp32 trunk GraphedTrainStep.is_fp32_trunk accepts: layers
+    1-4 that functions/codenet_units_fp32 refuses, or a tail that `_fp32_tail_outside_scope` refuses."""
+    from ..functions import codenet_units_fp32
+    with torch.enable_grad():      # (a property of the modules, as is_fp32_tail)
+        for name in ("layer1", "layer2", "layer3", "layer4"):
+            why = codenet_units_fp32.native_reason(getattr(net, name), None)
+            if why is not None:
+                return "%s: %s" % (name, why)
+    return _fp32_tail_outside_scope(net)
+
+
 class GraphedTrainStep:
     """One training step -- forward, loss, backward, optimizer -- over static input buffers as ONE HIP graph.
 
@@ -144,7 +156,12 @@ class GraphedTrainStep:
     ``pipeline.DetectionTail(model)`` of an fp32 model: those blocks in front of the fp32 detection heads [Conv2d 1x1,
     BatchNorm2d, ReLU, depthwise Conv2d 3x3, BatchNorm2d, ReLU, Conv2d 1x1] on functions/codenet_heads_fp32.py, every
     BatchNorm in training or eval mode (`is_fp32_tail`; tests/test_gpu_heads_fp32.py shows its
-    replays with the native criterion bit-identical to the eager steps).
+    replays with the native criterion bit-identical to the eager steps); and (7) the fp32 trunk,
+    ``pipeline.DetectionTrunk(model)`` of an fp32 model: layers 1-3 of ``harness.BaseNode`` units and layer4 [Conv2d 1x1,
+    BatchNorm2d, ReLU] on functions/codenet_units_fp32.py in front of that tail, from layer0's output, every BatchNorm in
+    training or eval mode (`is_fp32_trunk`; tests/test_gpu_units_fp32.py shows its replays with the
+    native criterion bit-identical to the eager steps).  The fp32 stem is not native: ``pipeline.DetectionNet`` of an fp32
+    model still needs `unvalidated=True`.
     tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
     bit-identical from a restored state whatever else the process does in between (a second model built before the capture
     taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
@@ -168,7 +185,7 @@ class GraphedTrainStep:
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
         if not unvalidated and not self.is_stage_stack(net) and not self.is_fp32_stage_stack(net) \
                 and not self.is_native_tail(net) and not self.is_native_trunk(net) and not self.is_native_net(net) \
-                and not self.is_fp32_tail(net):
+                and not self.is_fp32_tail(net) and not self.is_fp32_trunk(net):
             raise NotImplementedError(
                 "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for the "
                 "fp32 stack (a pipeline.DeconvLayers of [deform stage, BatchNorm2d, ReLU, Upsample] blocks on functions/codenet_bn), for a "
@@ -179,7 +196,13 @@ class GraphedTrainStep:
                 + (" [%s]" % _outside_scope(net) if isinstance(net, _DetectionChain) else "")
                 + " Also validated: the fp32 tail, a pipeline.DetectionTail of an fp32 model whose [deform stage, BatchNorm2d, "
                 "ReLU, Upsample] blocks run on functions/codenet_bn and whose heads run on functions/codenet_heads_fp32"
-                + (" [%s]" % _fp32_tail_outside_scope(net) if isinstance(net, DetectionTail) else "") + ".")
+                + (" [%s]" % _fp32_tail_outside_scope(net) if isinstance(net, DetectionTail) else "")
+                + ", and the fp32 trunk, a pipeline.DetectionTrunk of an fp32 model whose layers 1-4 also run on "
+                "functions/codenet_units_fp32"
+                + (" [%s]" % _fp32_trunk_outside_scope(net) if isinstance(net, DetectionTrunk) else "")
+                + (" [layer0: the fp32 stem (Conv2d 3 -> 24, BatchNorm2d, ReLU) has no native training path; capture "
+                   "pipeline.DetectionTrunk on layer0's output]"
+                   if isinstance(net, DetectionNet) and type(net.layer0[0]) is nn.Conv2d else "") + ".")
         self.static = [t.detach().clone() for t in example_inputs]
         for t, src in zip(self.static, example_inputs):
             t.requires_grad_(src.requires_grad)
@@ -234,6 +257,16 @@ class GraphedTrainStep:
         width, no hooks, NATIVE_FP32_HEADS on), every BatchNorm in training or eval mode.  A property of the modules: the
         caller's grad mode does not change the answer.  `is_native_tail` stays False for it."""
         return isinstance(net, DetectionTail) and _fp32_tail_outside_scope(net) is None
+
+    @staticmethod
+    def is_fp32_trunk(net):
+        """True for a pipeline.DetectionTrunk of an fp32 model: a tail that `is_fp32_tail` would accept (the same stages and
+        heads) behind layers 1-3 and layer4 that functions/codenet_units_fp32 runs natively (native_reason(layer, None) is
+        None: exactly ``harness.BaseNode`` units of nn.Conv2d / nn.BatchNorm2d in the reference's geometry and layer4 =
+        [Conv2d 1x1, BatchNorm2d, ReLU], no conv bias, affine BatchNorms that track running statistics with a float
+        momentum, no hooks, NATIVE_FP32_UNITS on), every BatchNorm in training or eval mode.  A property of the modules: the
+        caller's grad mode does not change the answer.  `is_native_trunk` stays False for it."""
+        return isinstance(net, DetectionTrunk) and _fp32_trunk_outside_scope(net) is None
 
     @staticmethod
     def is_native_tail(net):

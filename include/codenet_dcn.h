@@ -1293,6 +1293,73 @@ int cdn_codenet_head_fp32_bn_backward2(const float *g_z, const float *y, const f
                                        void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The fp32 ShuffleNetV2 units under autograd (lib/models/networks/shufflenetv2_dcn.py:57-114; layers 1-3 of main.py's
+ * model); codenet_units_fp32_train.hip; DESIGN.md section 4.3g states the arithmetic: every float32 operation rounded on its
+ * own, every sum in float64 in one order, no float atomics.  Per unit:
+ *   stride 1:  x1 = x[:, :h] (unchanged)                  x2 = x[:, h:]
+ *   stride 2:  y4 = dw3x3_s2(x, W4)   z4 = bn4(y4)        y5 = pw(z4, W5)   x1 = relu(bn5(y5))     x2 = x
+ *   both:      y1 = pw(x2, W1)        a1 = relu(bn1(y1))  y2 = dw3x3_s(a1, W2)   z2 = bn2(y2)
+ *              y3 = pw(z2, W3)        out[:, 2j] = x1[:, j],  out[:, 2j+1] = relu(bn3(y3))[:, j]
+ * The dense 1x1 convolutions and their gradients are cdn_codenet_pointwise_forward(_pitched) / cdn_codenet_pointwise_wgrad
+ * (_pitched), the statistics of every BatchNorm cdn_codenet_head_fp32_bn_stats, the second backward pass of BatchNorm1 / 3 /
+ * 5 cdn_codenet_head_fp32_bn_backward2; these are the pieces in between.  All tensors float32 NCHW, n = N H W values per
+ * channel; mean, invstd, mb, mg, gamma, beta are [C]; an "image pitch" is the distance in elements between two images of a
+ * tensor (a channel slice x[:, a:b] of [N][Cx][H][W] is (x + a * H * W, pitch Cx * H * W)).  Ho = (H - 1) / stride + 1.
+ * Never stored: a1 = relu(bn1(y1)), the unmasked grad_a1, grad_y2 / grad_y4 and the outputs of BatchNorm3 / 5 outside out.
+ * cdn_codenet_unit_fp32_workspace_bytes: the workspace of a call below on an [N][C][H][W] tensor (the depthwise backward: its
+ *   INPUT shape; the join backward: [N][h][H][W]): round_up_256(8 * max(C * slabs * 2, N * C * chunks * 11)), slabs =
+ *   ceil(n / 4096), chunks = ceil(items / min(256, round_up_64(items))), items = ceil(W / 4) * ceil(H / 8); 0 for arguments
+ *   the calls refuse.
+ * cdn_codenet_unit_fp32_dw_forward: out [N][C][Ho][Wo] = dw3x3(a, w [C][9], stride 1 or 2, zero padding 1), out = ((0 + w[0]
+ *   a[0]) + w[1] a[1]) + .. + w[8] a[8], taps row-major.  mean != NULL (with invstd, gamma, beta): a = relu(gamma * ((in - mean)
+ *   * invstd) + beta) formed on load, 0 outside the plane; all four NULL: a = in as it is.  in is read through its image pitch.
+ * cdn_codenet_unit_fp32_bn_forward: z = gamma * ((y - mean) * invstd) + beta, no ReLU (behind a depthwise), stored.
+ * cdn_codenet_unit_fp32_join_forward (replaces BatchNorm apply + ReLU + cat + channel_shuffle): out [N][2h][H][W]: out[:, 2j +
+ *   slot] = relu(bn(y [N][h][H][W]))[:, j]; x1 != NULL (slot 1 only): out[:, 2j] = x1[:, j] read at x1 + n * x1_image_pitch +
+ *   j * H * W.
+ * cdn_codenet_unit_fp32_join_backward: g_z [N][h][H][W] = grad_out[:, 2j + slot] where z > 0 else 0, z recomputed from y as in
+ *   the forward; grad_beta = f32(T1), grad_gamma = f32(T2), mb = f32(T1 / n), mg = f32(T2 / n) with T1 = sum g_z, T2 = sum g_z
+ *   xh; grad_x1 != NULL (slot 1 only): grad_x1 + n * pitch + j * H * W = grad_out[:, 2j].
+ * cdn_codenet_unit_fp32_bn_backward_sums: the same four per-channel results for a BatchNorm without ReLU: g_z is grad_z itself.
+ * cdn_codenet_unit_fp32_dw_backward: grad_y = ((grad_z - mb2) - xh2 mg2) * (gamma2 * invstd2) (training2 != 0) or grad_z *
+ *   (gamma2 * invstd2) formed on load from grad_z, y [N][C][Ho][Wo], 0 outside the plane.  grad_a[Y][X] = the sum, from zero
+ *   in row-major tap order, of w[dy][dx] grad_y[yo][xo] over the taps with Y + 1 - dy = stride * yo, X + 1 - dx = stride * xo
+ *   (a gather).  mean1 != NULL (branch 2; in = y1): grad_in = grad_a where z1 > 0 else 0 (= g_z1, required), grad_beta1,
+ *   grad_gamma1, mb1, mg1 from T1 = sum g_z1, T2 = sum g_z1 xh1.  mean1 == NULL (branch 1; in = x as it is; the other
+ *   BatchNorm1 arguments NULL): grad_in (may be NULL) = grad_a, accumulate != 0: ADDED to what is stored there, by the one
+ *   thread that owns the pixel.  grad_w [C][9] = f32(sum grad_y[p] a[stride p + t - 1]).
+ * Every call takes a stream, allocates nothing, launches no memset node and is capturable.  The workspace is the caller's,
+ * 16-byte aligned, every word written before it is read (CDN_ERR_WORKSPACE when too small).  16-byte accesses where the width
+ * of a tensor is a multiple of 4 and its pointer and pitch are 16-byte aligned, scalar ones otherwise: the same terms in the
+ * same order.  Sizes below 2^31 elements per tensor, pitches included (CDN_ERR_UNSUPPORTED beyond).  Argument errors are
+ * returned before any HIP call.  Everything written is OVERWRITTEN (but grad_in with accumulate).
+ * ---------------------------------------------------------------------------------------- */
+size_t cdn_codenet_unit_fp32_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W);
+int cdn_codenet_unit_fp32_dw_forward(const float *in, int64_t in_image_pitch, const float *mean, const float *invstd,
+                                     const float *gamma, const float *beta, const float *w, float *out, int64_t N, int64_t C,
+                                     int64_t H, int64_t W, int stride, void *stream);
+int cdn_codenet_unit_fp32_bn_forward(const float *y, const float *mean, const float *invstd, const float *gamma,
+                                     const float *beta, float *z, int64_t N, int64_t C, int64_t H, int64_t W, void *stream);
+int cdn_codenet_unit_fp32_join_forward(const float *y, const float *mean, const float *invstd, const float *gamma,
+                                       const float *beta, float *out, int slot, const float *x1, int64_t x1_image_pitch,
+                                       int64_t N, int64_t h, int64_t H, int64_t W, void *stream);
+int cdn_codenet_unit_fp32_join_backward(const float *grad_out, const float *y, const float *mean, const float *invstd,
+                                        const float *gamma, const float *beta, float *g_z, float *grad_gamma, float *grad_beta,
+                                        float *mb, float *mg, int slot, float *grad_x1, int64_t grad_x1_image_pitch, int64_t N,
+                                        int64_t h, int64_t H, int64_t W, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+int cdn_codenet_unit_fp32_bn_backward_sums(const float *grad_z, const float *y, const float *mean, const float *invstd,
+                                           float *grad_gamma, float *grad_beta, float *mb, float *mg, int64_t N, int64_t C,
+                                           int64_t H, int64_t W, void *workspace, size_t workspace_bytes, void *stream);
+int cdn_codenet_unit_fp32_dw_backward(const float *grad_z, const float *y, const float *mean2, const float *invstd2,
+                                      const float *gamma2, const float *mb2, const float *mg2, int training2, const float *in,
+                                      int64_t in_image_pitch, const float *mean1, const float *invstd1, const float *gamma1,
+                                      const float *beta1, const float *w, float *grad_in, int64_t grad_in_image_pitch,
+                                      int accumulate, float *grad_w, float *grad_gamma1, float *grad_beta1, float *mb1,
+                                      float *mg1, int64_t N, int64_t C, int64_t H, int64_t W, int stride, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

@@ -100,6 +100,11 @@ BUDGET_HEADS_FP32_TRAIN = {"head32_dw_fwd_kernel": 64, "head32_tail_fwd_kernel":
                            "head32_tail_bwd_kernelILi": 64, "head32_bn_bwd2_kernel": 64, "head32_tail_bwd_finish_kernel": 64,
                            "head32_dw_bwd_finish_kernel": 64, "bn_stats_kernel": 64, "bn_bwd1_kernelILi1": 64,
                            "bn_stats_finish_kernel": 64, "bn_bwd_finish_kernel": 64, "bn_eval_stats_kernel": 64}
+# codenet_units_fp32_train.hip (the fp32 units in training), from the compiled code: the depthwise
+# forward 37-62 VGPRs (the scalar stride-2 loader is the widest), the apply / join kernels 21-30, the first backward pass
+# 22-36, the depthwise backward 62-93 (stride 1 on the raw input is the widest); no scratch, no spills
+BUDGET_UNITS_FP32_TRAIN = {"unit32_dw_fwd_kernel": 64, "unit32_apply_kernel": 32, "unit32_bwd1_kernel": 40,
+                           "unit32_dw_bwd_kernelILi": 96, "unit32_dw_bwd_finish_kernel": 32}
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
     with tempfile.TemporaryDirectory() as tmp:
@@ -140,7 +145,8 @@ def check():
                                ("codenet_units_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_TRAIN),
                                ("codenet_stem_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_TRAIN),
                                ("codenet_bn_train.hip", ("-fno-slp-vectorize",), BUDGET_BN_TRAIN),
-                               ("codenet_heads_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_FP32_TRAIN)):
+                               ("codenet_heads_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_FP32_TRAIN),
+                               ("codenet_units_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_FP32_TRAIN)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -167,7 +173,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN) + list(BUDGET_HEADS_FP32_TRAIN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN) + list(BUDGET_HEADS_FP32_TRAIN) + list(BUDGET_UNITS_FP32_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))
