@@ -199,6 +199,12 @@ _SIGNATURES = {
     "cdn_codenet_unit_fp32_bn_backward_sums": (_i, [_vp] * 8 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
     "cdn_codenet_unit_fp32_dw_backward": (_i, [_vp] * 7 + [_i, _vp, _i64] + [_vp] * 5 + [_vp, _i64, _i] + [_vp] * 5
                                           + [_i64] * 4 + [_i, _vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_stem_fp32_workspace_bytes": (ctypes.c_size_t, [_i64] * 4),
+    "cdn_codenet_stem_fp32_pool_forward": (_i, [_vp] * 6 + [_i64] * 4 + [_vp]),
+    "cdn_codenet_stem_fp32_pool_backward": (_i, [_vp] * 11 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_stem_fp32_bn_relu_backward_sums": (_i, [_vp] * 10 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_stem_fp32_wgrad_workspace_bytes": (ctypes.c_size_t, [_i64] * 3 + [_i]),
+    "cdn_codenet_stem_fp32_wgrad": (_i, [_vp, _i] + [_vp] * 9 + [_i64] * 4 + [_i, _i, _vp, ctypes.c_size_t, _vp]),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

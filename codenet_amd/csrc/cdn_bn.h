@@ -215,9 +215,10 @@ bn_apply_kernel(const float *__restrict__ y, const float *__restrict__ mean, con
 
 // ------------------------------------------------------------------------------------------------------
 // bn_bwd1_kernel: g_z of one (channel, slab) at stored resolution and the partial T1 = sum g_z, T2 = sum g_z * xh.
-// g: [N][C][H][W] (UP == 1) or [N][C][2H][2W] (UP == 2).  part [C][slabs][2].
+// g: [N][C][H][W] (UP == 1) or [N][C][2H][2W] (UP == 2).  part [C][slabs][2].  !STORE: only the sums, gz is not written (the
+// un-pooled fp32 stem, whose weight gradient forms the mask on load).
 // ------------------------------------------------------------------------------------------------------
-template <int UP, bool VEC>
+template <int UP, bool VEC, bool STORE = true>
 __global__ void __launch_bounds__(kBnThreads)
 bn_bwd1_kernel(const float *__restrict__ g, const float *__restrict__ y, const float *__restrict__ mean,
                const float *__restrict__ invstd, const float *__restrict__ gamma, const float *__restrict__ beta,
@@ -262,7 +263,7 @@ bn_bwd1_kernel(const float *__restrict__ g, const float *__restrict__ y, const f
         t1 = t1 + (double)o[e];
         t2 = t2 + (double)o[e] * (double)xh;
       }
-      *reinterpret_cast<float4 *>(gz + off) = make_float4(o[0], o[1], o[2], o[3]);
+      if (STORE) *reinterpret_cast<float4 *>(gz + off) = make_float4(o[0], o[1], o[2], o[3]);
     } else {
       cnt = n - j0 < 4 ? (int)(n - j0) : 4;
 #pragma unroll
@@ -282,7 +283,7 @@ bn_bwd1_kernel(const float *__restrict__ g, const float *__restrict__ y, const f
           float xh;
           const float z = bn_z(y[off], p, xh);
           const float o = z > 0.0f ? Ge : 0.0f;
-          gz[off] = o;
+          if (STORE) gz[off] = o;
           t1 = t1 + (double)o;
           t2 = t2 + (double)o * (double)xh;
         }

@@ -1,6 +1,7 @@
 // cdn_train.h -- what the kernels of the QAT step share (codenet_heads_train.hip, codenet_units_train.hip,
 // codenet_stem_train.hip): the fake-quantiser of a state snapshot, the register-window row loaders
-// of the depthwise kernels and the one protocol of the per-channel weight / bias gradient sums.
+// of the depthwise kernels and the one protocol of the per-channel weight / bias gradient sums; and what the two stems share
+// (codenet_stem_train.hip, codenet_stem_fp32_train.hip): the 27-tap patch loader and the plan of the weight gradient.
 //
 // The sums.  A workgroup's K sums belong to one channel (group): a thread adds its own terms in its own fixed order, the 64
 // lanes of a wave by an xor shuffle tree (32, 16, .. 1), the waves in wave order through LDS, and the workgroup stores its K
@@ -9,7 +10,27 @@
 #pragma once
 #include "cdn_common.h"
 
+#include <algorithm>
+
 namespace cdn {
+
+// The 3 -> 24 stem (codenet_stem_train.hip, codenet_stem_fp32_train.hip): 3 input channels x 3 x 3 taps per output position,
+// and the plan of its weight gradient -- chunks of 256 * per_thread consecutive output positions (n, oy, ox flattened),
+// per_thread = clamp(positions / 1024, 1, 8).  The chunk order is part of grad_W's contract in both files.
+constexpr int kStemTaps = 27;
+struct StemPlan {
+  int Ho, Wo, per_thread, chunks;
+  long positions;
+};
+inline StemPlan stem_plan(int64_t N, int64_t H, int64_t W, int stride) {
+  StemPlan p;
+  p.Ho = (int)((H - 1) / stride + 1);
+  p.Wo = (int)((W - 1) / stride + 1);
+  p.positions = (long)N * p.Ho * p.Wo;
+  p.per_thread = (int)std::min<long>(8, std::max<long>(1, p.positions / 1024));
+  p.chunks = (int)ceil_div(p.positions, 256L * p.per_thread);
+  return p;
+}
 
 // grad_w [C][K - 1] and grad_b [C] (either may be NULL) from the workgroups' partials
 // [outer][C / G][chunks][G][K] -- K sums per channel: K - 1 taps and the bias, G channels per workgroup -- summed outer
@@ -18,6 +39,23 @@ int launch_sums_reduce(const float *part, float *grad_w, float *grad_b, int C, i
                        hipStream_t st, const char *what);
 
 #ifdef __HIPCC__
+// the 27 taps of the stem's output position (oy, ox) of image n in (ci, dy, dx) order, zero outside the image
+__device__ __forceinline__ void load_stem_patch(const float *__restrict__ img, int n, int oy, int ox, int H, int W,
+                                                int stride, float (&v)[kStemTaps]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        // (guarded loads, not clamped addresses masked afterwards: the inference stem_kernel of codenet_layers.hip measured
+        // the clamped form slower, 78-90 us against 61-62 us)
+        const int y = oy * stride + dy - 1, x = ox * stride + dx - 1;
+        v[(c * 3 + dy) * 3 + dx] = ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W)
+                                       ? img[(((long)n * 3 + c) * H + y) * W + x] : 0.0f;
+      }
+}
+
 // scale, zero point and RN(1 / scale) of a QuantAct state (snapshot): the operands of fake_quant_r
 struct Fq {
   float s, z, r;

@@ -18,12 +18,10 @@
 // per channel group, six times in all, through L2.
 #include "cdn_train.h"
 
-#include <algorithm>
-
 namespace {
 
 constexpr int kStCo = 24;                         // output channels of the stem
-constexpr int kStTaps = 27;                       // 3 input channels x 3 x 3
+constexpr int kStTaps = cdn::kStemTaps;           // 3 input channels x 3 x 3
 constexpr int kStGroup = 4;                       // output channels per workgroup of the weight gradient
 constexpr int kStSums = kStTaps + 1;              // per channel: 27 taps of grad_w and grad_b
 constexpr int kStPart = kStGroup * kStSums;       // partial sums a workgroup stores
@@ -31,23 +29,6 @@ constexpr int kStPart = kStGroup * kStSums;       // partial sums a workgroup st
 using cdn::Fq;
 using cdn::fq_relu;
 using cdn::load_fq;
-
-// the 27 taps of output position (oy, ox) of image n in (ci, dy, dx) order, zero outside the image
-__device__ __forceinline__ void load_patch(const float *__restrict__ img, int n, int oy, int ox, int H, int W, int stride,
-                                           float (&v)[kStTaps]) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        // (guarded loads, not clamped addresses masked afterwards: the inference stem_kernel of codenet_layers.hip measured
-        // the clamped form slower, 78-90 us against 61-62 us)
-        const int y = oy * stride + dy - 1, x = ox * stride + dx - 1;
-        v[(c * 3 + dy) * 3 + dx] = ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W)
-                                       ? img[(((long)n * 3 + c) * H + y) * W + x] : 0.0f;
-      }
-}
 
 // ------------------------------------------------------------------------------------------------------
 // stem_train_fwd_kernel: y0 = conv3x3(img, w [24][27], stride, zero padding 1) + b, the RAW output, NCHW.  One lane per
@@ -69,7 +50,7 @@ stem_train_fwd_kernel(const float *__restrict__ img, const float *__restrict__ w
   if (p < HW) {
     const int oy = p / Wo, ox = p - oy * Wo;
     float v[kStTaps];
-    load_patch(img, n, oy, ox, H, W, stride, v);
+    cdn::load_stem_patch(img, n, oy, ox, H, W, stride, v);
     float *dst = y0 + (long)n * kStCo * HW + p;
 #pragma unroll
     for (int co = 0; co < kStCo; ++co) {
@@ -220,7 +201,7 @@ stem_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ y0, con
       const int n = (int)(pidx / HW), p = (int)(pidx - (long)n * HW);
       const int oy = p / Wo, ox = p - oy * Wo;
       float v[kStTaps];
-      load_patch(img, n, oy, ox, H, W, stride, v);
+      cdn::load_stem_patch(img, n, oy, ox, H, W, stride, v);
       const long o = ((long)n * kStCo + grp * kStGroup) * HW + p;
 #pragma unroll
       for (int e = 0; e < kStGroup; ++e) {
@@ -235,19 +216,8 @@ stem_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ y0, con
   cdn::block_sums_store(sums, red, part);
 }
 
-struct StPlan {
-  int Ho, Wo, per_thread, chunks;
-  long positions;
-};
-StPlan stem_plan(int64_t N, int64_t H, int64_t W, int stride) {
-  StPlan p;
-  p.Ho = (int)((H - 1) / stride + 1);
-  p.Wo = (int)((W - 1) / stride + 1);
-  p.positions = (long)N * p.Ho * p.Wo;
-  p.per_thread = (int)std::min<long>(8, std::max<long>(1, p.positions / 1024));
-  p.chunks = (int)cdn::ceil_div(p.positions, 256L * p.per_thread);
-  return p;
-}
+using StPlan = cdn::StemPlan;
+using cdn::stem_plan;
 
 }  // namespace
 

@@ -175,8 +175,12 @@ def native_reason(layer0, x):
 
 def forward_stem(layer0, x, keep=None):
     """``layer0(x)`` for the stem.  In the QAT step on the GPU (native_reason(layer0, x) is None) it runs as one
-    CodenetStemFunction; otherwise exactly ``layer0(x)``.  keep (tests): a dict that receives the native path's own y0, the
-    state snapshot, the pooled flag and -- after the backward of a pooled stem -- gy0."""
+    CodenetStemFunction; an fp32 stem that codenet_stem_fp32.native_reason accepts runs as one CodenetStemFp32Function;
+    otherwise exactly ``layer0(x)``.  keep (tests): a dict that receives the native path's own y0, the state snapshot, the
+    pooled flag and -- after the backward of a pooled stem -- gy0 (the fp32 function: see its docstring)."""
+    from . import codenet_stem_fp32 as S32
+    if S32.native_reason(layer0, x) is None:
+        return S32.forward_fp32_stem(layer0, x, keep)
     if native_reason(layer0, x) is not None:
         return layer0(x)
     cb, act, pool = _split(layer0)

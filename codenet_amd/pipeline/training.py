@@ -124,6 +124,41 @@ def _fp32_trunk_outside_scope(net):
     return _fp32_tail_outside_scope(net)
 
 
+def _fp32_stem_reason(net, example_inputs):
+    """None, or the reason why the fp32 stem of `net`, a DetectionNet, would not run natively on the example image: the gate
+    of functions/codenet_stem_fp32 on the modules AND on the image the capture will see -- an image that requires grad,
+    lives on the CPU or is not float32 contiguous would silently put the stem back on the framework's backward."""
+    from ..functions import codenet_stem_fp32
+    with torch.enable_grad():
+        why = codenet_stem_fp32.native_reason(net.layer0, None)
+        if why is not None:
+            return why
+        if not example_inputs:
+            return "no example image to judge"
+        return codenet_stem_fp32.native_reason(net.layer0, example_inputs[0])
+
+
+def _fp32_net_outside_scope(net):
+    """None, or the reason why `net`, a DetectionNet, is not the fp32 network GraphedTrainStep.is_fp32_net accepts: a stem
+    that functions/codenet_stem_fp32 refuses, or a trunk that `_fp32_trunk_outside_scope` refuses."""
+    from ..functions import codenet_stem_fp32
+    with torch.enable_grad():      # (a property of the modules, as is_fp32_trunk)
+        why = codenet_stem_fp32.native_reason(net.layer0, None)
+    return "layer0: %s" % why if why is not None else _fp32_trunk_outside_scope(net)
+
+
+def _fp32_net_reason(net, example_inputs):
+    """The bracket of the constructor's error for `net`, a DetectionNet: for an fp32 stem (its first module is a Conv2d) what
+    the stem's gate says about the modules and the example image, behind "layer0: the fp32 stem: "; where the stem is
+    accepted, or is no fp32 stem at all, the reason of `_fp32_net_outside_scope` (the trunk's, or the stem's structure)."""
+    l0 = net.layer0
+    if isinstance(l0, nn.Sequential) and len(l0) and type(l0[0]) is nn.Conv2d:
+        why = _fp32_stem_reason(net, example_inputs)
+        if why is not None:
+            return "layer0: the fp32 stem: %s" % why
+    return _fp32_net_outside_scope(net)
+
+
 class GraphedTrainStep:
     """One training step -- forward, loss, backward, optimizer -- over static input buffers as ONE HIP graph.
 
@@ -160,8 +195,12 @@ class GraphedTrainStep:
     ``pipeline.DetectionTrunk(model)`` of an fp32 model: layers 1-3 of ``harness.BaseNode`` units and layer4 [Conv2d 1x1,
     BatchNorm2d, ReLU] on functions/codenet_units_fp32.py in front of that tail, from layer0's output, every BatchNorm in
     training or eval mode (`is_fp32_trunk`; tests/test_gpu_units_fp32.py shows its replays with the
-    native criterion bit-identical to the eager steps).  The fp32 stem is not native: ``pipeline.DetectionNet`` of an fp32
-    model still needs `unvalidated=True`.
+    native criterion bit-identical to the eager steps); and (8) the fp32 network, ``pipeline.DetectionNet(model)`` of an fp32
+    model: the stem [Conv2d 3 -> 24, BatchNorm2d, ReLU(, MaxPool2d(3, 2, 1))] on functions/codenet_stem_fp32.py in front of
+    that trunk, from the image, every BatchNorm in training or eval mode (`is_fp32_net`; DESIGN.md section 4.3h;
+    tests/test_gpu_stem_fp32.py shows its replays with the native criterion bit-identical to the eager steps) -- accepted
+    when the gate also accepts the example image (a float32, contiguous GPU image that does not require grad): main.py's
+    whole step, image -> loss -> optimizer, is then one chain of this library's kernels.
     tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
     bit-identical from a restored state whatever else the process does in between (a second model built before the capture
     taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
@@ -185,7 +224,8 @@ class GraphedTrainStep:
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
         if not unvalidated and not self.is_stage_stack(net) and not self.is_fp32_stage_stack(net) \
                 and not self.is_native_tail(net) and not self.is_native_trunk(net) and not self.is_native_net(net) \
-                and not self.is_fp32_tail(net) and not self.is_fp32_trunk(net):
+                and not self.is_fp32_tail(net) and not self.is_fp32_trunk(net) \
+                and not (self.is_fp32_net(net) and _fp32_stem_reason(net, example_inputs) is None):
             raise NotImplementedError(
                 "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for the "
                 "fp32 stack (a pipeline.DeconvLayers of [deform stage, BatchNorm2d, ReLU, Upsample] blocks on functions/codenet_bn), for a "
@@ -200,9 +240,9 @@ class GraphedTrainStep:
                 + ", and the fp32 trunk, a pipeline.DetectionTrunk of an fp32 model whose layers 1-4 also run on "
                 "functions/codenet_units_fp32"
                 + (" [%s]" % _fp32_trunk_outside_scope(net) if isinstance(net, DetectionTrunk) else "")
-                + (" [layer0: the fp32 stem (Conv2d 3 -> 24, BatchNorm2d, ReLU) has no native training path; capture "
-                   "pipeline.DetectionTrunk on layer0's output]"
-                   if isinstance(net, DetectionNet) and type(net.layer0[0]) is nn.Conv2d else "") + ".")
+                + ", and the fp32 network, a pipeline.DetectionNet of an fp32 model whose stem also runs on "
+                "functions/codenet_stem_fp32 for the example image"
+                + (" [%s]" % _fp32_net_reason(net, example_inputs) if isinstance(net, DetectionNet) else "") + ".")
         self.static = [t.detach().clone() for t in example_inputs]
         for t, src in zip(self.static, example_inputs):
             t.requires_grad_(src.requires_grad)
@@ -267,6 +307,16 @@ class GraphedTrainStep:
         momentum, no hooks, NATIVE_FP32_UNITS on), every BatchNorm in training or eval mode.  A property of the modules: the
         caller's grad mode does not change the answer.  `is_native_trunk` stays False for it."""
         return isinstance(net, DetectionTrunk) and _fp32_trunk_outside_scope(net) is None
+
+    @staticmethod
+    def is_fp32_net(net):
+        """True for a pipeline.DetectionNet of an fp32 model: a trunk that `is_fp32_trunk` would accept (the same layers 1-4,
+        stages and heads) behind a stem that functions/codenet_stem_fp32 runs natively (native_reason(layer0, None) is None:
+        exactly Sequential(Conv2d 3 -> 24 3x3 without bias, BatchNorm2d, ReLU[, MaxPool2d(3, 2, 1)]) at stride 2 with the pool
+        or 4 without, an affine BatchNorm that tracks running statistics with a float momentum, no hooks, NATIVE_FP32_STEM
+        on).  A property of the modules: the caller's grad mode does not change the answer.  The constructor also judges the
+        example image (`_fp32_stem_reason`).  `is_native_net` stays False for it."""
+        return isinstance(net, DetectionNet) and _fp32_net_outside_scope(net) is None
 
     @staticmethod
     def is_native_tail(net):

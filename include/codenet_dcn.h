@@ -1360,6 +1360,56 @@ int cdn_codenet_unit_fp32_dw_backward(const float *grad_z, const float *y, const
                                       size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The fp32 stem under autograd (layer0 of main.py's model: Conv2d(3, 24, 3, stride 4 | 2, padding 1, bias=False) ->
+ * BatchNorm2d -> ReLU [-> MaxPool2d(3, 2, 1)]); codenet_stem_fp32_train.hip; DESIGN.md section 4.3h states the arithmetic:
+ * every float32 operation rounded on its own, T1 / T2 in float64 in one order, no float atomics.  The raw convolution y0 is
+ * cdn_codenet_stem_train_forward with b = NULL and running = 0, its statistics cdn_codenet_head_fp32_bn_stats, the un-pooled
+ * stem's output cdn_codenet_bn_relu_up_forward with up = 1; these are the pieces in between.  All tensors float32 NCHW; y0 is
+ * [N][C][H][W] (H, W: ITS size, not the image's), n = N H W values per channel; mean, invstd, mb, mg, gamma, beta are [C];
+ * Hp = (H - 1) / 2 + 1.  Never stored: a0 = relu(bn(y0)), the ReLU mask, grad_y0 and, without the pool, g_z.
+ * cdn_codenet_stem_fp32_workspace_bytes: the workspace of the two backward calls on y0: round_up_256(C * slabs * 16), slabs =
+ *   ceil(n / 4096); 0 for arguments the calls refuse, shapes of 2^31 elements or more included.
+ * cdn_codenet_stem_fp32_pool_forward: out [N][C][Hp][Wp] = max over the 3x3 window, stride 2, padding 1, clipped at the
+ *   borders, of a0 = relu(gamma * ((y0 - mean) * invstd) + beta) formed on load: the winner of `val > max || isnan(val)` from
+ *   -inf in row-major scan order (a NaN in the window wins).
+ * cdn_codenet_stem_fp32_pool_backward: from g [N][C][Hp][Wp]: a window's gradient goes to its first maximum in that scan
+ *   order, compared on a0 formed on load; a pixel adds the windows it won in row-major window order from 0.0f (a gather, every
+ *   element written exactly once); g_z [N][C][H][W] = that sum where z > 0 else 0 (stored); grad_beta = f32(T1), grad_gamma =
+ *   f32(T2), mb = f32(T1 / n), mg = f32(T2 / n) with T1 = sum g_z, T2 = sum g_z xh, the (channel, slab) sums of
+ *   cdn_codenet_bn_relu_up_backward.
+ * cdn_codenet_stem_fp32_bn_relu_backward_sums: the same four per-channel results for the un-pooled stem: g [N][C][H][W] is
+ *   grad_out, g_z = g where z > 0 else 0 is formed on load; nothing of tensor size is written.
+ * cdn_codenet_stem_fp32_wgrad (N, H, W: the IMAGE's size; Co must be 24, stride 2 or 4; Ho = (H - 1) / stride + 1): grad_w
+ *   [24][27] = sum grad_y0[n][c][oy][ox] img[n][ci][oy S + dy - 1][ox S + dx - 1] (zero outside the image) with grad_y0 =
+ *   ((g_z - mb) - xh mg) * (gamma * invstd) (training != 0) or g_z * (gamma * invstd) (training == 0: mb / mg not read) formed
+ *   on load from g, y0 [N][24][Ho][Wo]; masked != 0: g is g_z (the pool backward's); masked == 0: g is grad_out and g_z = g
+ *   where z > 0 else 0.  float32 fma in the decomposition and chunk order of cdn_codenet_stem_backward; OVERWRITTEN.
+ *   cdn_codenet_stem_fp32_wgrad_workspace_bytes: the size cdn_codenet_stem_backward_workspace_bytes gives; 0 for arguments the
+ *   call refuses, an image or a y0 of 2^31 elements or more included.
+ * Every call takes a stream, allocates nothing, launches no memset node and is capturable.  The workspace is the caller's,
+ * 16-byte aligned, every word written before it is read (CDN_ERR_WORKSPACE when too small).  16-byte accesses where the width
+ * of a tensor is a multiple of 4 and its pointer is 16-byte aligned, scalar ones otherwise: the same terms in the same order.
+ * Sizes below 2^31 elements per tensor (CDN_ERR_UNSUPPORTED beyond).  Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+size_t cdn_codenet_stem_fp32_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W);
+int cdn_codenet_stem_fp32_pool_forward(const float *y0, const float *mean, const float *invstd, const float *gamma,
+                                       const float *beta, float *out, int64_t N, int64_t C, int64_t H, int64_t W,
+                                       void *stream);
+int cdn_codenet_stem_fp32_pool_backward(const float *g, const float *y0, const float *mean, const float *invstd,
+                                        const float *gamma, const float *beta, float *g_z, float *grad_gamma, float *grad_beta,
+                                        float *mb, float *mg, int64_t N, int64_t C, int64_t H, int64_t W, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+int cdn_codenet_stem_fp32_bn_relu_backward_sums(const float *g, const float *y0, const float *mean, const float *invstd,
+                                                const float *gamma, const float *beta, float *grad_gamma, float *grad_beta,
+                                                float *mb, float *mg, int64_t N, int64_t C, int64_t H, int64_t W,
+                                                void *workspace, size_t workspace_bytes, void *stream);
+size_t cdn_codenet_stem_fp32_wgrad_workspace_bytes(int64_t N, int64_t H, int64_t W, int stride);
+int cdn_codenet_stem_fp32_wgrad(const float *g, int masked, const float *y0, const float *img, const float *mean,
+                                const float *invstd, const float *gamma, const float *beta, const float *mb, const float *mg,
+                                float *grad_w, int64_t N, int64_t H, int64_t W, int64_t Co, int stride, int training,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

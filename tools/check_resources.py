@@ -105,6 +105,12 @@ BUDGET_HEADS_FP32_TRAIN = {"head32_dw_fwd_kernel": 64, "head32_tail_fwd_kernel":
 # 22-36, the depthwise backward 62-93 (stride 1 on the raw input is the widest); no scratch, no spills
 BUDGET_UNITS_FP32_TRAIN = {"unit32_dw_fwd_kernel": 64, "unit32_apply_kernel": 32, "unit32_bwd1_kernel": 40,
                            "unit32_dw_bwd_kernelILi": 96, "unit32_dw_bwd_finish_kernel": 32}
+# codenet_stem_fp32_train.hip (the fp32 stem in training), from the compiled code: the pool forward
+# with its 3 x 9 window 41-54 VGPRs, the first backward pass without the pool (cdn_bn.h's bn_bwd1_kernel without its store)
+# 22-28, with the pool 52 (the per-pixel gather) and 81 (the 5 x 7 patch of the 16-byte path); the weight gradient holds
+# codenet_stem_train.hip's 4 x 28 sums beside the 27-value patch (160, three waves per SIMD); no scratch, no spills
+BUDGET_STEM_FP32_TRAIN = {"stem32_pool_fwd_kernel": 64, "stem32_pool_bwd_kernel": 96, "bn_bwd1_kernelILi1": 64,
+                          "stem32_wgrad_kernel": 168}
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
     with tempfile.TemporaryDirectory() as tmp:
@@ -146,7 +152,8 @@ def check():
                                ("codenet_stem_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_TRAIN),
                                ("codenet_bn_train.hip", ("-fno-slp-vectorize",), BUDGET_BN_TRAIN),
                                ("codenet_heads_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_FP32_TRAIN),
-                               ("codenet_units_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_FP32_TRAIN)):
+                               ("codenet_units_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_FP32_TRAIN),
+                               ("codenet_stem_fp32_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_FP32_TRAIN)):
         res_x = kernel_resources(src, extra)
         for frag, cap in budget.items():
             hits = [(n, r) for n, r in res_x.items() if frag in n]
@@ -173,7 +180,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN) + list(BUDGET_HEADS_FP32_TRAIN) + list(BUDGET_UNITS_FP32_TRAIN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN) + list(BUDGET_HEADS_FP32_TRAIN) + list(BUDGET_UNITS_FP32_TRAIN) + list(BUDGET_STEM_FP32_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))

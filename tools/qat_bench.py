@@ -74,13 +74,11 @@ def replay_s(step, steps):
     return (time.perf_counter() - t0) / steps
 
 
-def captured_step(net, example, config, res=512, steps=20):
-    """The captured QAT step of `net` (a pipeline.Detection* wrapper) on the input `example` -- losses.CtdetLoss on fixed
-    targets at res / 4, fused capturable Adam -- as pipeline.GraphedTrainStep accepts it without `unvalidated`, timed over
-    `steps` replays.  Prints and returns one JSON line under `config`."""
-    from codenet_amd import pipeline
+def ctdet_setup(batch, res):
+    """(crit, targets): losses.CtdetLoss with the default options and fixed targets of 25-50 objects per image on the
+    res / 4 maps -- what every captured-step timing of these tools trains against."""
     from codenet_amd.losses import CtdetLoss, ctdet_targets
-    batch, R, M = example.shape[0], res // 4, 50
+    R, M = res // 4, 50
     rng = np.random.default_rng(1)
     c = rng.uniform([1, 1], [R - 2, R - 2], (batch, M, 2))
     s = rng.uniform(0.8, 40.0, (batch, M, 2))
@@ -89,6 +87,16 @@ def captured_step(net, example, config, res=512, steps=20):
                             torch.from_numpy(rng.integers(M // 2, M + 1, batch)).cuda(), 20, R, R, M)
     crit = CtdetLoss(types.SimpleNamespace(mse_loss=False, reg_loss="l1", dense_wh=False, norm_wh=False, cat_spec_wh=False,
                                            num_stacks=1, hm_weight=1.0, wh_weight=0.1, off_weight=1.0, reg_offset=True))
+    return crit, targets
+
+
+def captured_step(net, example, config, res=512, steps=20):
+    """The captured QAT step of `net` (a pipeline.Detection* wrapper) on the input `example` -- losses.CtdetLoss on fixed
+    targets at res / 4, fused capturable Adam -- as pipeline.GraphedTrainStep accepts it without `unvalidated`, timed over
+    `steps` replays.  Prints and returns one JSON line under `config`."""
+    from codenet_amd import pipeline
+    batch = example.shape[0]
+    crit, targets = ctdet_setup(batch, res)
     opt = torch.optim.Adam(net.parameters(), lr=torch.tensor(1.25e-4, device="cuda"), capturable=True, fused=True)
     step = pipeline.GraphedTrainStep(net, opt, lambda n, f: crit(n(f), targets)[0], (example,), warmup=3)
     dt = replay_s(step, steps)
