@@ -157,6 +157,11 @@ _SIGNATURES = {
     "cdn_ctdet_merge_scales": (_i, [_vp, _vp] + [_i64] * 4 + [_i, _i, _f, _f, _f, _i] + [_vp] * 6),
     "cdn_ctdet_pre_process": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i, _vp]),
     "cdn_ctdet_pre_process_aug": (_i, [_vp, _vp, _i64] + [_vp] * 5 + [_i64, _i64, _vp]),
+    "cdn_jpeg_parse": (_i, [_vp, _i64, _vp]),
+    "cdn_jpeg_pack": (_i, [_vp, _i64, ctypes.c_int32, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "cdn_jpeg_workspace_bytes": (ctypes.c_size_t, [_i64] * 3),
+    "cdn_jpeg_decode": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp]),
+    "cdn_jpeg_decode_host": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i]),
     "cdn_ctdet_loss_workspace_bytes": (ctypes.c_size_t, [_i64] * 5 + [_i]),
     "cdn_ctdet_loss_forward": (_i, [_vp] * 8 + [_i64] * 5 + [_i] * 3 + [_f] * 3 + [_vp] * 3 + [ctypes.c_size_t, _vp]),
     "cdn_ctdet_loss_backward": (_i, [_vp] * 8 + [_i64] * 5 + [_i] * 2 + [_f] * 3 + [_vp] * 6),

@@ -6,7 +6,8 @@ image bytes and a per-item table from device memory.
 
 The arithmetic is an integer specification of this project, in the form of cv2.resize +
 cv2.warpAffine(INTER_LINEAR) on uint8; it is exact and tested bit for bit against a numpy restatement
-(tests/preproc_ref.py).  It makes no claim about cv2's own bits.  Not here: JPEG decoding, keep_res.
+(tests/preproc_ref.py).  It makes no claim about cv2's own bits.  Not here: keep_res.  The image bytes may come from the
+GPU JPEG decoder (codenet_amd/jpeg.py: JpegPreProcess decodes into the arena and load_table() commits the rows).
 
 PreProcess(..., color_aug=True) is the training mode with the reference's default colour augmentation
 (sample/ctdet.py:76-79, lib/utils/image.py:196-234; cdn_ctdet_pre_process_aug): the crop's bytes and their exact integer
@@ -213,14 +214,10 @@ class PreProcess:
             self._commit(rows)
         return metas
 
-    def load_items(self, arena_bytes, table, aug=None):
-        """The batched (training) form: arena_bytes = uint8 bytes that hold several images, table = [n][16] rows as
-        item_row() builds them (any offset, pitch, matrix and flip_src; ratio_y / ratio_x are recomputed here).  Every
-        row is checked against the bytes given before anything is copied.  aug (color_aug=True only): one aug row per
-        item (aug_row(), color_aug_params(), AUG_OFF); None = every item off."""
+    def check_table(self, nbytes, table, aug=None):
+        """What load_items and load_table check before anything is copied: -> (rows, aug rows) or ValueError."""
         if aug is not None and not self.color_aug:
             raise ValueError("aug= needs PreProcess(..., color_aug=True)")
-        nbytes = int(np.prod(arena_bytes.shape))
         table = np.asarray(table, dtype=np.float64).reshape(-1, ITEM)
         if nbytes > self.capacity or not 0 < len(table) <= self.max_items:
             raise ValueError("%d bytes / %d items are beyond the capacity (%d bytes, %d items)"
@@ -239,9 +236,27 @@ class PreProcess:
             rows.append(item_row(off, h, w, pitch, r[9:15], new_h, new_w, r[8] != 0.0))
         if aug is not None:
             aug = check_aug(aug, len(rows))
+        return rows, aug
+
+    def load_items(self, arena_bytes, table, aug=None):
+        """The batched (training) form: arena_bytes = uint8 bytes that hold several images, table = [n][16] rows as
+        item_row() builds them (any offset, pitch, matrix and flip_src; ratio_y / ratio_x are recomputed here).  Every
+        row is checked against the bytes given before anything is copied.  aug (color_aug=True only): one aug row per
+        item (aug_row(), color_aug_params(), AUG_OFF); None = every item off."""
+        nbytes = int(np.prod(arena_bytes.shape))
+        rows, aug = self.check_table(nbytes, table, aug)
         with torch.cuda.device(self.device):
             self._reuse_pinned()
             self._bytes(arena_bytes, nbytes)
+            self._commit(rows, aug)
+
+    def load_table(self, nbytes, table, aug=None):
+        """load_items without the bytes: commits the item rows (and aug rows) for `nbytes` bytes that are ALREADY in
+        self.arena, or that work queued on the current stream writes there before run() -- jpeg.JpegDecoder.run(pre.arena).
+        The rows are checked against nbytes exactly as load_items checks them; nothing is copied when one is refused."""
+        rows, aug = self.check_table(int(nbytes), table, aug)
+        with torch.cuda.device(self.device):
+            self._reuse_pinned()
             self._commit(rows, aug)
 
     # ---- launch ----------------------------------------------------------------------------------------------------------

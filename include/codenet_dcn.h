@@ -997,6 +997,57 @@ int cdn_ctdet_pre_process_aug(const unsigned char *src_arena, const double *item
                               int64_t out_h, int64_t out_w, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Baseline JPEG decoding in front of the pre-processing: file bytes -> interleaved uint8 pixels with the bits of
+ * libjpeg-turbo's default decode (ISLOW IDCT, fancy up-sampling, 16-bit fixed-point YCbCr -> RGB: what cv2.imread and PIL
+ * give; EXIF orientation is ignored, as PIL does).  codenet_jpeg.hip + cdn_jpeg.h; Python: codenet_amd/jpeg.py.  The
+ * arithmetic is DESIGN.md section 7.4d (tests/jpeg_ref.py restates it in numpy; both equal PIL bit for bit).
+ * Supported: SOF0, 8-bit samples and quantisation tables, one interleaved scan, 1 or 3 components, every component 1x1
+ * or Y 2x1 / 2x2 with 1x1 chroma, restart intervals.  Everything else (progressive, arithmetic, 12-bit, 16-bit tables,
+ * CMYK, 4:4:0, 4:1:1, several scans, DNL, RGB-coded) is CDN_ERR_UNSUPPORTED from the two host functions.
+ *
+ * Records (int32, little-endian, written by cdn_jpeg_pack):
+ *   item [16]    {w, h, components, mode (0 all 1x1, 1 Y 2x1, 2 Y 2x2), mcus_x, mcus_y, table selectors, Y pitch, Y rows,
+ *                 C pitch, C rows, restart interval, output offset low / high word, output pitch, 0}
+ *   segment [8]  {item, first MCU, MCU count, byte offset into the stream buffer, byte length, 0, 0, 0}; record 0 of the
+ *                segment buffer is the header {segments used, items used, 0...}, the segments follow it
+ *   tables       6144 bytes per item: 3 x 64 quantisation bytes per COMPONENT in natural order, then the decode form of
+ *                the Huffman tables DC 0, DC 1, AC 0, AC 1 (struct cdn_jpeg::Tables)
+ *
+ * cdn_jpeg_parse (host, no HIP call): info[16] = {w, h, components, mode, mcus_x, mcus_y, restart interval, segments,
+ *   offset of the entropy-coded data, 0...}.  Malformed data: CDN_ERR_ARG.
+ * cdn_jpeg_pack (host, no HIP call): parses `data` again and, in one pass over its entropy-coded bytes, removes the
+ *   stuffed 00 after every FF and cuts the bytes at RSTn / EOI into segments; writes the bytes at stream + stream_used,
+ *   the records behind the segs_used segments already there, the item record and the table blob of item `item` (the
+ *   caller passes the addresses of that item's slots) and the header record; used[0] / used[1] = the new byte / segment
+ *   counts.  A missing EOI ends the last segment at the end of the data.  CDN_ERR_WORKSPACE when a capacity (stream
+ *   bytes, segments, plane_stride for the image's padded planes) is too small: detected before anything is written.
+ * cdn_jpeg_workspace_bytes: the planes of max_items images of at most max_h x max_w; per item
+ *   plane_stride = cdn_jpeg_workspace_bytes(1, max_h, max_w) bytes.  0: a size outside 1..65535.
+ * cdn_jpeg_decode: two launches on `stream`, capturable -- jpeg_entropy_idct_kernel (segments -> uint8 component planes,
+ *   padded to whole MCUs) and jpeg_color_kernel (planes -> out + offset + y pitch + 3 x, B G R, or R G B with rgb != 0).
+ *   Every pointer is DEVICE memory.  The launch geometry follows from seg_cap, item_cap and plane_stride alone and the
+ *   counts are read from the header record, so a captured call replays for any batch inside the capacities.  The kernels
+ *   check every record against stream_cap / seg_cap / item_cap / plane_stride / out_cap before they store.
+ *   status [item_cap] int32, zeroed by the caller: per item the maximum of 0 ok, 1 bits were consumed beyond the end of a
+ *   segment, 2 a code with no entry in its Huffman table, 3 a record outside the capacities (integer atomicMax: the order
+ *   cannot change the bits).  The pixels of an item with a non-zero status are unspecified.
+ *   Concurrency: a segment is decoded by ONE lane; the entropy kernel scales with batch size x restart intervals.
+ * cdn_jpeg_decode_host: the same call with HOST pointers; runs the same decoder text on the calling thread, no HIP call.
+ * Argument errors are returned before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_jpeg_parse(const unsigned char *data, int64_t n, int32_t *info);
+int cdn_jpeg_pack(const unsigned char *data, int64_t n, int32_t item, int64_t out_off, int64_t out_pitch,
+                  unsigned char *stream_bytes, int64_t stream_used, int64_t stream_cap, int32_t *segs, int64_t segs_used,
+                  int64_t seg_cap, int32_t *item_rec, unsigned char *tables, int64_t plane_stride, int64_t *used);
+size_t cdn_jpeg_workspace_bytes(int64_t max_items, int64_t max_h, int64_t max_w);
+int cdn_jpeg_decode(const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs, int64_t seg_cap,
+                    const int32_t *items, int64_t item_cap, const unsigned char *tables, unsigned char *planes,
+                    int64_t plane_stride, int32_t *status, unsigned char *out, int64_t out_cap, int rgb, void *stream);
+int cdn_jpeg_decode_host(const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs, int64_t seg_cap,
+                         const int32_t *items, int64_t item_cap, const unsigned char *tables, unsigned char *planes,
+                         int64_t plane_stride, int32_t *status, unsigned char *out, int64_t out_cap, int rgb);
+
+/* ------------------------------------------------------------------------------------------
  * The ctdet training criterion (main.py / quant_main.py: ModelWithLoss -> CtdetLoss, lib/trains/ctdet.py:17-74) and
  * the target maps it is fed (lib/datasets/sample/ctdet.py:87-122).  codenet_loss.hip; Python: codenet_amd/losses.py.
  *
