@@ -1,9 +1,13 @@
-// cdn_bn.h -- the BatchNorm2d kernels of the fp32 training path (DESIGN.md sections 4.3e and 4.3f), shared by
-// codenet_bn_train.hip (the block behind a deform stage) and codenet_heads_fp32_train.hip (the detection heads): bn_z, the
-// per-channel operands, the float64 (channel, slab) sums and the statistics / apply / first- and second-pass backward kernels
-// with their launch plan.  The head of codenet_bn_train.hip states the arithmetic and the order of the sums.  Everything is in
-// an unnamed namespace: a file that includes this header holds its own copy, compiled with that file's flags.  The including
-// file is built with -fno-slp-vectorize; `#pragma clang fp contract(off)` below holds to the end of the translation unit.
+// cdn_bn.h -- the BatchNorm2d kernels of the fp32 training path (DESIGN.md sections 4.3e to 4.3h), shared by
+// codenet_bn_train.hip (the block behind a deform stage), codenet_heads_fp32_train.hip (the detection heads),
+// codenet_units_fp32_train.hip (the ShuffleNetV2 units) and codenet_stem_fp32_train.hip (the stem): bn_z, the per-channel
+// operands, the second backward pass's expression (bn_grad_y), the float64 (channel, slab) sums and the statistics / apply /
+// first- and second-pass backward kernels with their launch plan and the two launch sequences every file repeats (statistics,
+// finish); and what the depthwise kernels of the heads and the units share: the window-row loader, the strip plan, the shape
+// check and the finish kernel of the depthwise backward.  The head of codenet_bn_train.hip states the arithmetic and the order
+// of the sums.  Everything is in an unnamed namespace: a file that includes this header holds its own copy, compiled with that
+// file's flags.  The including file is built with -fno-slp-vectorize; `#pragma clang fp contract(off)` below holds to the end
+// of the translation unit.
 #pragma once
 #include "cdn_train.h"
 
@@ -38,24 +42,60 @@ __device__ __forceinline__ float bn_z(float y, const BnCh &p, float &xh) {
   return s + p.beta;
 }
 
-// two float64 sums of a workgroup -> part[blockIdx.x][2]; every thread calls it.  red: 2 doubles of LDS per wave.
-__device__ __forceinline__ void block_sums_store_f64(double a, double b, double *red, double *__restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// The second backward pass: its per-channel operands and grad_y = ((g_z - mb) - xh * mg) * (gamma * invstd) (SUB: batch
+// statistics) or g_z * (gamma * invstd) (!SUB: eval mode; mb, mg and y are not read).  Every kernel that forms grad_y -- the
+// two second-pass kernels, the depthwise backward kernels on load, the stem's weight gradient -- forms it here.
+struct BnBwd2 {
+  float mean, invstd, k, mb, mg;
+};
+template <bool SUB>
+__device__ __forceinline__ BnBwd2 load_bwd2(const float *__restrict__ mean, const float *__restrict__ invstd,
+                                            const float *__restrict__ gamma, const float *__restrict__ mb,
+                                            const float *__restrict__ mg, int c) {
+  BnBwd2 q;
+  q.mean = mean[c];
+  q.invstd = invstd[c];
+  q.k = gamma[c] * q.invstd;
+  q.mb = SUB ? mb[c] : 0.0f;
+  q.mg = SUB ? mg[c] : 0.0f;
+  return q;
+}
+template <bool SUB>
+__device__ __forceinline__ float bn_grad_y(float gz, float y, const BnBwd2 &q) {
+  if (!SUB) return gz * q.k;
+  const float d = y - q.mean;
+  const float xh = d * q.invstd;
+  const float t1 = gz - q.mb;
+  const float t2 = xh * q.mg;
+  const float t3 = t1 - t2;
+  return t3 * q.k;
+}
+
+// One window row (NC columns from xa - 1) of a depthwise input.  BN: a = relu(bn_z(v)) inside the plane, literal zeros
+// outside (the convolution's padding -- NOT relu(bn_z(0))); returns the mask of z > 0 (the ReLU mask of the backward); xh4
+// (may be NULL): xh of the columns xa .. xa + 3.  !BN: the stored values as they are (zeros outside); returns the mask of
+// the columns inside.
+template <int NC, bool BN, bool VEC>
+__device__ __forceinline__ unsigned load_win(const float *__restrict__ plane, int y, int H, int W, int xa, const BnCh &p,
+                                             float (&a)[NC], float *xh4 = nullptr) {
+  float v[NC];
+  const unsigned ok = cdn::load_cols<NC, 1, VEC>(plane, y, H, W, xa, v);
+  if (!BN) {
 #pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    a += __shfl_xor(a, m, 64);
-    b += __shfl_xor(b, m, 64);
+    for (int j = 0; j < NC; ++j) a[j] = v[j];
+    return ok;
   }
-  if (lane == 0) {
-    red[wave * 2] = a;
-    red[wave * 2 + 1] = b;
+  unsigned pos = 0u;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const bool in = (ok >> j) & 1u;
+    float xh;
+    const float z = bn_z(v[j], p, xh);
+    a[j] = in ? cdn::relu_keep_nan(z) : 0.0f;
+    pos |= (in && z > 0.0f) ? (1u << j) : 0u;
+    if (xh4 && j >= 1 && j <= 4) xh4[j - 1] = xh;
   }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    double s = red[threadIdx.x];
-    for (int i = 1; i < kBnThreads / 64; ++i) s += red[i * 2 + threadIdx.x];
-    part[(long)blockIdx.x * 2 + threadIdx.x] = s;
-  }
+  return pos;
 }
 
 // offset of value j of channel c in an [N][C][HW] tensor.  (Every index of these kernels lies below 2^31, bn_check_shape:
@@ -97,7 +137,7 @@ bn_stats_kernel(const float *__restrict__ y, double *__restrict__ part, int C, i
         s2 = s2 + dv * dv;
       }
   }
-  block_sums_store_f64(s1, s2, red, part);
+  cdn::block_sums_store({s1, s2}, red, part);
 }
 
 // f32 of 1 / sqrt(v), both correctly rounded in float32 (see the head of the file)
@@ -289,7 +329,7 @@ bn_bwd1_kernel(const float *__restrict__ g, const float *__restrict__ y, const f
         }
     }
   }
-  block_sums_store_f64(t1, t2, red, part);
+  cdn::block_sums_store({t1, t2}, red, part);
 }
 
 // one thread per channel: grad_beta, grad_gamma (either may be NULL) and the two means of the second pass
@@ -325,9 +365,7 @@ bn_bwd2_kernel(const float *gz, const float *__restrict__ y, const float *__rest
     const long r = (unsigned)i / (unsigned)Wq;
     const int w0 = (int)((unsigned)i - (unsigned)r * (unsigned)Wq) * 4;
     const int c = (int)(((unsigned)r / (unsigned)H) % (unsigned)C);
-    const float mu = mean[c], is = invstd[c];
-    const float k = gamma[c] * is;
-    const float b = SUB ? mb[c] : 0.0f, a = SUB ? mg[c] : 0.0f;
+    const BnBwd2 q = load_bwd2<SUB>(mean, invstd, gamma, mb, mg, c);
     const long off = r * W + w0;
     const int cnt = (VEC || W - w0 > 4) ? 4 : W - w0;
     float v[4], z[4], o[4];
@@ -346,18 +384,7 @@ bn_bwd2_kernel(const float *gz, const float *__restrict__ y, const float *__rest
       }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (SUB) {
-        const float d = v[e] - mu;
-        const float xh = d * is;
-        const float t1 = z[e] - b;
-        const float t2 = xh * a;
-        const float t3 = t1 - t2;
-        o[e] = t3 * k;
-      } else {
-        o[e] = z[e] * k;
-      }
-    }
+    for (int e = 0; e < 4; ++e) o[e] = bn_grad_y<SUB>(z[e], SUB ? v[e] : 0.0f, q);
     if (VEC) {
       *reinterpret_cast<float4 *>(gy + off) = make_float4(o[0], o[1], o[2], o[3]);
     } else {
@@ -391,6 +418,99 @@ int bn_check_shape(int64_t N, int64_t C, int64_t H, int64_t W, int up) {
 
 unsigned rows_grid(long rows, int64_t W) {
   return (unsigned)std::max<long>(1, std::min<long>(cdn::ceil_div(rows * cdn::ceil_div(W, 4), 256), (long)cdn::kCUs * 16));
+}
+
+// The statistics of y [N][C][H][W] behind the caller's pointer and shape checks: mean, var, invstd from the batch (training:
+// part = workspace, of at least `need` bytes; the running buffers and the counter updated) or from the running statistics.
+// The caller checks the launches.
+int launch_bn_stats(const float *y, float *running_mean, float *running_var, int64_t *num_batches_tracked, float *mean,
+                    float *var, float *invstd, int64_t N, int64_t C, int64_t H, int64_t W, int training, double eps,
+                    double momentum, void *workspace, size_t workspace_bytes, size_t need, hipStream_t st) {
+  CDN_REQUIRE(eps >= 0.0, CDN_ERR_ARG, "eps must not be negative");
+  const unsigned cgrid = (unsigned)cdn::ceil_div(C, 64);
+  if (!training) {
+    CDN_REQUIRE(running_mean && running_var, CDN_ERR_ARG, "eval mode needs the running statistics");
+    bn_eval_stats_kernel<<<cgrid, 64, 0, st>>>(running_mean, running_var, mean, var, invstd, (int)C, (float)eps);
+    return CDN_OK;
+  }
+  CDN_REQUIRE(N * H * W > 1, CDN_ERR_ARG, "batch statistics need more than one value per channel");
+  CDN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), CDN_ERR_ARG, "one running buffer without the other");
+  CDN_REQUIRE(momentum >= 0.0 && momentum <= 1.0, CDN_ERR_ARG, "momentum must lie in [0, 1]");
+  CDN_REQUIRE(workspace, CDN_ERR_ARG, "null workspace");
+  if (int rc = cdn::check_workspace(workspace, workspace_bytes, need)) return rc;
+  const BnPlan p = bn_plan(N, C, H, W);
+  double *part = static_cast<double *>(workspace);
+  const unsigned grid = (unsigned)(C * p.slabs);
+  if (W % 4 == 0 && cdn::aligned16(y))
+    bn_stats_kernel<true><<<grid, kBnThreads, 0, st>>>(y, part, (int)C, (int)(H * W), p.n, p.slabs);
+  else
+    bn_stats_kernel<false><<<grid, kBnThreads, 0, st>>>(y, part, (int)C, (int)(H * W), p.n, p.slabs);
+  bn_stats_finish_kernel<<<cgrid, 64, 0, st>>>(part, mean, var, invstd, running_mean, running_var,
+                                               reinterpret_cast<long long *>(num_batches_tracked), (int)C, p.slabs, p.n,
+                                               (float)eps, (float)momentum, (float)(1.0 - momentum));
+  return CDN_OK;
+}
+
+// behind a first-pass kernel that left part [C][slabs][2]
+void launch_bn_bwd_finish(const double *part, float *grad_gamma, float *grad_beta, float *mb, float *mg, int64_t C,
+                          const BnPlan &p, hipStream_t st) {
+  bn_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C, 64), 64, 0, st>>>(part, grad_gamma, grad_beta, mb, mg, (int)C, p.slabs, p.n);
+}
+
+// ---- what the depthwise kernels of the heads and the units share ----------------------------------------------------------
+constexpr int kStripRows = 8;      // rows of a thread's strip
+constexpr int kDwSums = 11;        // per-plane sums of a depthwise backward: nine taps of grad_w, T1, T2
+
+// a thread owns a strip of kStripRows rows x 4 columns of an H x W plane; a workgroup a chunk of `threads` strips of one plane
+struct StripPlan {
+  int wq, strips, threads, chunks;
+};
+StripPlan strip_plan(int64_t H, int64_t W) {
+  StripPlan p;
+  p.wq = (int)cdn::ceil_div(W, 4);
+  p.strips = (int)cdn::ceil_div(H, kStripRows);
+  const long items = (long)p.wq * p.strips;
+  p.threads = (int)std::min<long>(256, cdn::ceil_div(items, 64) * 64);
+  p.chunks = (int)cdn::ceil_div(items, p.threads);
+  return p;
+}
+
+// [N][C][H][W] tensors of the heads and the units: positive sizes, 32-bit indexing, grids below 2^31
+int train32_check_shape(int64_t N, int64_t C, int64_t H, int64_t W) {
+  CDN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, CDN_ERR_ARG, "non-positive size");
+  CDN_REQUIRE(N * C * H * W < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
+  CDN_REQUIRE(C * cdn::ceil_div(N * H * W, kBnSlab) < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
+  CDN_REQUIRE(N * C * strip_plan(H, W).chunks < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
+  return CDN_OK;
+}
+
+// bytes of the partials [N][C][chunks][kDwSums] of a depthwise backward
+size_t dw_part_bytes(int64_t N, int64_t C, int64_t H, int64_t W) {
+  return (size_t)N * (size_t)C * (size_t)strip_plan(H, W).chunks * kDwSums * sizeof(double);
+}
+
+// one thread per (channel, sum): the partials [N][C][chunks][11] added in index order (images, then chunks); leaves
+// grad_w [C][9] and (grad_gamma != NULL) grad_gamma, grad_beta and the two means of BatchNorm1's second pass
+__global__ void __launch_bounds__(256)
+dw_bwd_finish_kernel(const double *__restrict__ part, float *__restrict__ grad_w, float *__restrict__ grad_gamma,
+                     float *__restrict__ grad_beta, float *__restrict__ mb, float *__restrict__ mg, int N, int C, int chunks,
+                     long n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= C * kDwSums) return;
+  const int c = i / kDwSums, k = i % kDwSums;
+  if (k >= 9 && !grad_gamma) return;
+  double s = 0.0;
+  for (int img = 0; img < N; ++img)
+    for (int h = 0; h < chunks; ++h) s = s + part[(((long)img * C + c) * chunks + h) * kDwSums + k];
+  if (k < 9) {
+    grad_w[c * 9 + k] = (float)s;
+  } else if (k == 9) {
+    grad_beta[c] = (float)s;
+    mb[c] = (float)(s / (double)n);
+  } else {
+    grad_gamma[c] = (float)s;
+    mg[c] = (float)(s / (double)n);
+  }
 }
 
 }  // namespace

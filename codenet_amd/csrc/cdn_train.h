@@ -141,21 +141,22 @@ __device__ __forceinline__ unsigned load_act(const float *__restrict__ plane, in
   return RQ ? pos : ok;
 }
 
-// The end of a weight-gradient kernel (see the head of the file); every thread of the workgroup calls it.  red: K floats
-// of LDS per wave; part [workgroups][K]: workgroup blockIdx.x stores its K words.
-template <int K>
-__device__ __forceinline__ void block_sums_store(const float (&sums)[K], float *red, float *__restrict__ part) {
+// The end of a weight-gradient kernel (see the head of the file); every thread of the workgroup calls it.  red: K words
+// of LDS per wave; part [workgroups][K]: workgroup blockIdx.x stores its K words.  T: float here, double in the fp32
+// training path (cdn_bn.h).
+template <int K, typename T>
+__device__ __forceinline__ void block_sums_store(const T (&sums)[K], T *red, T *__restrict__ part) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    float v = sums[k];
+    T v = sums[k];
 #pragma unroll
     for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
     if (lane == 0) red[wave * K + k] = v;
   }
   __syncthreads();
   if (threadIdx.x < K) {
-    float s = red[threadIdx.x];
+    T s = red[threadIdx.x];
     for (int i = 1; i < nw; ++i) s += red[i * K + threadIdx.x];
     part[(long)blockIdx.x * K + threadIdx.x] = s;
   }

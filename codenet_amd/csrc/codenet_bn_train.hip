@@ -29,7 +29,7 @@
 // thread per channel) adds a channel's partials in slab order and finishes the per-channel numbers.  No float atomics.
 // W % 4 == 0 (VEC): a quad lies in one row and moves as 16-byte words; otherwise element by element -- the same terms in the
 // same order either way.
-// The kernels live in cdn_bn.h (the fp32 detection heads run the same ones, codenet_heads_fp32_train.hip).
+// The kernels live in cdn_bn.h (the fp32 heads, units and stem run the same ones, codenet_*_fp32_train.hip).
 #include "cdn_bn.h"
 
 #pragma clang fp contract(off)
@@ -47,29 +47,10 @@ extern "C" int cdn_codenet_bn_relu_up_forward(const float *y, const float *gamma
   CDN_REQUIRE(y && gamma && beta && mean && var && invstd && out, CDN_ERR_ARG, "null pointer");
   if (int rc = bn_check_shape(N, C, H, W, up)) return rc;
   CDN_REQUIRE(cdn::aligned16(y) && cdn::aligned16(out), CDN_ERR_ARG, "tensors must be 16-byte aligned");
-  CDN_REQUIRE(eps >= 0.0, CDN_ERR_ARG, "eps must not be negative");
   hipStream_t st = cdn::as_stream(stream);
-  const unsigned cgrid = (unsigned)cdn::ceil_div(C, 64);
-  if (training) {
-    CDN_REQUIRE(N * H * W > 1, CDN_ERR_ARG, "batch statistics need more than one value per channel");
-    CDN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), CDN_ERR_ARG, "one running buffer without the other");
-    CDN_REQUIRE(momentum >= 0.0 && momentum <= 1.0, CDN_ERR_ARG, "momentum must lie in [0, 1]");
-    CDN_REQUIRE(workspace, CDN_ERR_ARG, "null workspace");
-    if (int rc = cdn::check_workspace(workspace, workspace_bytes, cdn_codenet_bn_workspace_bytes(N, C, H, W))) return rc;
-    const BnPlan p = bn_plan(N, C, H, W);
-    double *part = static_cast<double *>(workspace);
-    const unsigned grid = (unsigned)(C * p.slabs);
-    if (W % 4 == 0)
-      bn_stats_kernel<true><<<grid, kBnThreads, 0, st>>>(y, part, (int)C, (int)(H * W), p.n, p.slabs);
-    else
-      bn_stats_kernel<false><<<grid, kBnThreads, 0, st>>>(y, part, (int)C, (int)(H * W), p.n, p.slabs);
-    bn_stats_finish_kernel<<<cgrid, 64, 0, st>>>(part, mean, var, invstd, running_mean, running_var,
-                                                 reinterpret_cast<long long *>(num_batches_tracked), (int)C, p.slabs, p.n,
-                                                 (float)eps, (float)momentum, (float)(1.0 - momentum));
-  } else {
-    CDN_REQUIRE(running_mean && running_var, CDN_ERR_ARG, "eval mode needs the running statistics");
-    bn_eval_stats_kernel<<<cgrid, 64, 0, st>>>(running_mean, running_var, mean, var, invstd, (int)C, (float)eps);
-  }
+  if (int rc = launch_bn_stats(y, running_mean, running_var, num_batches_tracked, mean, var, invstd, N, C, H, W, training, eps,
+                               momentum, workspace, workspace_bytes, cdn_codenet_bn_workspace_bytes(N, C, H, W), st))
+    return rc;
   const long rows = (long)(N * C * H);
   const unsigned grid = rows_grid(rows, W);
   const bool vec = W % 4 == 0;
@@ -109,8 +90,7 @@ extern "C" int cdn_codenet_bn_relu_up_backward(const float *grad_out, const floa
     if (vec) CDN_BN_BWD1(2, true); else CDN_BN_BWD1(2, false);
   }
 #undef CDN_BN_BWD1
-  bn_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C, 64), 64, 0, st>>>(part, grad_gamma, grad_beta, mb, mg, (int)C, p.slabs,
-                                                                      p.n);
+  launch_bn_bwd_finish(part, grad_gamma, grad_beta, mb, mg, C, p, st);
   const long rows = (long)(N * C * H);
   const unsigned grid2 = rows_grid(rows, W);
 #define CDN_BN_BWD2(SUB, VEC) \

@@ -32,48 +32,6 @@
 
 namespace {
 
-constexpr int kH32Rows = 8;       // rows of a thread's strip
-constexpr int kH32Sums = 11;      // per-plane sums of the depthwise backward: nine taps of grad_w2, T1, T2
-
-// K float64 sums of a workgroup -> part[blockIdx.x][K]; every thread calls it.  red: K doubles of LDS per wave.
-template <int K>
-__device__ __forceinline__ void block_sums_store_f64k(const double (&sums)[K], double *red, double *__restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double v = sums[k];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (lane == 0) red[wave * K + k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double s = red[threadIdx.x];
-    for (int i = 1; i < nw; ++i) s += red[i * K + threadIdx.x];
-    part[(long)blockIdx.x * K + threadIdx.x] = s;
-  }
-}
-
-// One window row (columns xa - 1 .. xa + 4) of a1 = relu(bn_z(y1)): literal zeros outside the plane.  Returns the mask of
-// z > 0 (the ReLU mask of the backward); xh (may be NULL): xh of the columns xa .. xa + 3.
-template <bool VEC>
-__device__ __forceinline__ unsigned load_a1(const float *__restrict__ plane, int y, int H, int W, int xa, const BnCh &p,
-                                            float (&a)[6], float *xh4) {
-  float v[6];
-  const unsigned ok = cdn::load_cols<6, 1, VEC>(plane, y, H, W, xa, v);
-  unsigned pos = 0u;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const bool in = (ok >> j) & 1u;
-    float xh;
-    const float z = bn_z(v[j], p, xh);
-    a[j] = in ? cdn::relu_keep_nan(z) : 0.0f;
-    pos |= (in && z > 0.0f) ? (1u << j) : 0u;
-    if (xh4 && j >= 1 && j <= 4) xh4[j - 1] = xh;
-  }
-  return pos;
-}
-
 // ------------------------------------------------------------------------------------------------------
 // head32_dw_fwd_kernel: y2 = dw3x3(relu(bn1(y1)), w2), zero padding 1, no bias; the strip layout of head_dw_fwd_kernel.
 // ------------------------------------------------------------------------------------------------------
@@ -89,7 +47,7 @@ head32_dw_fwd_kernel(const float *__restrict__ y1, const float *__restrict__ mea
   const int strip = (int)(t % strips);
   const long plane = t / strips;
   const int c = (int)(plane % C);
-  const int x0 = q * 4, ya = strip * kH32Rows, yb = min(H, ya + kH32Rows);
+  const int x0 = q * 4, ya = strip * kStripRows, yb = min(H, ya + kStripRows);
   const float *src = y1 + plane * H * W;
   float *dst = y2 + plane * H * W;
   const BnCh p = load_ch(mean, invstd, gamma, beta, c);
@@ -97,10 +55,10 @@ head32_dw_fwd_kernel(const float *__restrict__ y1, const float *__restrict__ mea
 #pragma unroll
   for (int k = 0; k < 9; ++k) w[k] = w2[c * 9 + k];
   float a[3][6];
-  load_a1<VEC>(src, ya - 1, H, W, x0, p, a[0], nullptr);
-  load_a1<VEC>(src, ya, H, W, x0, p, a[1], nullptr);
+  load_win<6, true, VEC>(src, ya - 1, H, W, x0, p, a[0]);
+  load_win<6, true, VEC>(src, ya, H, W, x0, p, a[1]);
   for (int y = ya; y < yb; ++y) {
-    load_a1<VEC>(src, y + 1, H, W, x0, p, a[2], nullptr);
+    load_win<6, true, VEC>(src, y + 1, H, W, x0, p, a[2]);
     float out[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -256,7 +214,7 @@ head32_tail_bwd_kernel(const float *__restrict__ g, const float *__restrict__ y2
         if (e < cnt) gz[ch_offset(j0 + e, c, C, HW)] = o4[e];
     }
   }
-  block_sums_store_f64k<K>(sums, red, part);
+  cdn::block_sums_store(sums, red, part);
 }
 
 // one thread per channel: adds the slabs' partials in slab order; grad_gamma2, grad_beta2, the two means of the second
@@ -290,7 +248,7 @@ head32_tail_bwd_finish_kernel(const double *__restrict__ part, float *__restrict
 // layout: a workgroup works on chunk blockIdx.x % chunks of the strips of ONE (n, c) plane).
 //   grad_y2 formed while loading g_z2 and y2 (SUB: batch statistics of BatchNorm2; !SUB: eval mode), 0 outside the plane
 //   grad_a1[q] = sum_t w2[c][t] grad_y2[q - t]       a GATHER over the nine neighbours with mirrored taps
-//   g_z1 = z1 > 0 ? grad_a1 : 0                       stored; z1, xh1 from load_a1's bn_z
+//   g_z1 = z1 > 0 ? grad_a1 : 0                       stored; z1, xh1 from load_win's bn_z
 //   part [N][C][chunks][11]: grad_W2[c][t] = sum_p grad_y2[p] a1[p + t], T1 = sum g_z1, T2 = sum g_z1 xh1 (float64)
 // ------------------------------------------------------------------------------------------------------
 template <bool SUB, bool VEC>
@@ -301,49 +259,34 @@ head32_dw_bwd_kernel(const float *__restrict__ gz2, const float *__restrict__ y2
                      const float *__restrict__ invstd1, const float *__restrict__ gamma1, const float *__restrict__ beta1,
                      const float *__restrict__ w2, float *__restrict__ gz1, double *__restrict__ part, int C, int H, int W,
                      int wq, int strips, int chunks) {
-  __shared__ double red[4 * kH32Sums];
+  __shared__ double red[4 * kDwSums];
   const int chunk = (int)(blockIdx.x % chunks);
   const long plane = blockIdx.x / chunks;
   const int c = (int)(plane % C);
   const int item = chunk * (int)blockDim.x + (int)threadIdx.x;
-  double sums[kH32Sums];
+  double sums[kDwSums];
 #pragma unroll
-  for (int k = 0; k < kH32Sums; ++k) sums[k] = 0.0;
+  for (int k = 0; k < kDwSums; ++k) sums[k] = 0.0;
   if (item < wq * strips) {
-    const int x0 = (item % wq) * 4, ya = (item / wq) * kH32Rows, yb = min(H, ya + kH32Rows);
+    const int x0 = (item % wq) * 4, ya = (item / wq) * kStripRows, yb = min(H, ya + kStripRows);
     const long HW = (long)H * W;
     const float *gsrc = gz2 + plane * HW, *y2src = y2 + plane * HW, *y1src = y1 + plane * HW;
     float *dst = gz1 + plane * HW;
     const BnCh p1 = load_ch(mean1, invstd1, gamma1, beta1, c);
-    const float mu2 = mean2[c], is2 = invstd2[c];
-    const float k2 = gamma2[c] * is2;
-    const float b2 = SUB ? mb2[c] : 0.0f, a2 = SUB ? mg2[c] : 0.0f;
+    const BnBwd2 q2 = load_bwd2<SUB>(mean2, invstd2, gamma2, mb2, mg2, c);
     float w[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) w[k] = w2[c * 9 + k];
     float gw[3][6], aw[3][6], xm[4], xn[4];      // xh1 of the middle and of the newest row
     unsigned pos[3];
-    // one window row: grad_y2 (bn_bwd2_kernel's expression), a1 with its mask z1 > 0 and xh1
+    // one window row: grad_y2 (bn_grad_y), a1 with its mask z1 > 0 and xh1
     auto load_row = [&](int y, float (&gr)[6], float (&ar)[6], float (&xr)[4], unsigned &pm) {
       float gv[6], yv[6];
       const unsigned ok = cdn::load_cols<6, 1, VEC>(gsrc, y, H, W, x0, gv);
       if (SUB) cdn::load_cols<6, 1, VEC>(y2src, y, H, W, x0, yv);
 #pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        float o;
-        if (SUB) {
-          const float d = yv[j] - mu2;
-          const float xh = d * is2;
-          const float t1 = gv[j] - b2;
-          const float t2 = xh * a2;
-          const float t3 = t1 - t2;
-          o = t3 * k2;
-        } else {
-          o = gv[j] * k2;
-        }
-        gr[j] = ((ok >> j) & 1u) ? o : 0.0f;
-      }
-      pm = load_a1<VEC>(y1src, y, H, W, x0, p1, ar, xr);
+      for (int j = 0; j < 6; ++j) gr[j] = ((ok >> j) & 1u) ? bn_grad_y<SUB>(gv[j], SUB ? yv[j] : 0.0f, q2) : 0.0f;
+      pm = load_win<6, true, VEC>(y1src, y, H, W, x0, p1, ar, xr);
     };
     load_row(ya - 1, gw[0], aw[0], xn, pos[0]);
     load_row(ya, gw[1], aw[1], xm, pos[1]);
@@ -383,30 +326,7 @@ head32_dw_bwd_kernel(const float *__restrict__ gz2, const float *__restrict__ y2
       pos[1] = pos[2];
     }
   }
-  block_sums_store_f64k<kH32Sums>(sums, red, part);
-}
-
-// one thread per (channel, sum): the partials [N][C][chunks][11] added in index order (images, then chunks); leaves
-// grad_W2 [C][9], grad_gamma1, grad_beta1 and the two means of BatchNorm1's second pass
-__global__ void __launch_bounds__(256)
-head32_dw_bwd_finish_kernel(const double *__restrict__ part, float *__restrict__ grad_w2, float *__restrict__ grad_gamma,
-                            float *__restrict__ grad_beta, float *__restrict__ mb, float *__restrict__ mg, int N, int C,
-                            int chunks, long n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * kH32Sums) return;
-  const int c = i / kH32Sums, k = i % kH32Sums;
-  double s = 0.0;
-  for (int img = 0; img < N; ++img)
-    for (int h = 0; h < chunks; ++h) s = s + part[(((long)img * C + c) * chunks + h) * kH32Sums + k];
-  if (k < 9) {
-    grad_w2[c * 9 + k] = (float)s;
-  } else if (k == 9) {
-    grad_beta[c] = (float)s;
-    mb[c] = (float)(s / (double)n);
-  } else {
-    grad_gamma[c] = (float)s;
-    mg[c] = (float)(s / (double)n);
-  }
+  cdn::block_sums_store(sums, red, part);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -427,9 +347,7 @@ head32_bn_bwd2_kernel(const float *__restrict__ gz, const float *__restrict__ y,
     const int h = (int)((unsigned)r - plane * (unsigned)H);
     const unsigned img = plane / (unsigned)C;
     const int c = (int)(plane - img * (unsigned)C);
-    const float mu = mean[c], is = invstd[c];
-    const float k = gamma[c] * is;
-    const float b = SUB ? mb[c] : 0.0f, a = SUB ? mg[c] : 0.0f;
+    const BnBwd2 q = load_bwd2<SUB>(mean, invstd, gamma, mb, mg, c);
     const long off = r * W + w0;
     float *dst = gy + (long)img * pitch + ((long)c * H + h) * W + w0;
     const int cnt = (VEC || W - w0 > 4) ? 4 : W - w0;
@@ -449,18 +367,7 @@ head32_bn_bwd2_kernel(const float *__restrict__ gz, const float *__restrict__ y,
       }
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (SUB) {
-        const float d = v[e] - mu;
-        const float xh = d * is;
-        const float t1 = z[e] - b;
-        const float t2 = xh * a;
-        const float t3 = t1 - t2;
-        o[e] = t3 * k;
-      } else {
-        o[e] = z[e] * k;
-      }
-    }
+    for (int e = 0; e < 4; ++e) o[e] = bn_grad_y<SUB>(z[e], SUB ? v[e] : 0.0f, q);
     if (VEC) {
       *reinterpret_cast<float4 *>(dst) = make_float4(o[0], o[1], o[2], o[3]);
     } else {
@@ -471,33 +378,10 @@ head32_bn_bwd2_kernel(const float *__restrict__ gz, const float *__restrict__ y,
   }
 }
 
-struct H32Plan {
-  int wq, strips, threads, chunks;
-};
-H32Plan head32_plan(int64_t H, int64_t W) {
-  H32Plan p;
-  p.wq = (int)cdn::ceil_div(W, 4);
-  p.strips = (int)cdn::ceil_div(H, kH32Rows);
-  const long items = (long)p.wq * p.strips;
-  p.threads = (int)std::min<long>(256, cdn::ceil_div(items, 64) * 64);
-  p.chunks = (int)cdn::ceil_div(items, p.threads);
-  return p;
-}
-
-// [N][C][H][W] tensors of the heads: positive sizes, 32-bit indexing, grids below 2^31
-int head32_check_shape(int64_t N, int64_t C, int64_t H, int64_t W) {
-  CDN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, CDN_ERR_ARG, "non-positive size");
-  CDN_REQUIRE(N * C * H * W < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
-  CDN_REQUIRE(C * cdn::ceil_div(N * H * W, kBnSlab) < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
-  CDN_REQUIRE(N * C * head32_plan(H, W).chunks < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
-  return CDN_OK;
-}
-
 size_t head32_ws_bytes(int64_t N, int64_t C, int64_t H, int64_t W) {
   const size_t slabs = (size_t)cdn::ceil_div(N * H * W, kBnSlab);
   const size_t tail = (size_t)C * slabs * 10 * sizeof(double);      // 2 + 2 Co sums, Co <= 4 (the statistics: 2)
-  const size_t dw = (size_t)N * (size_t)C * (size_t)head32_plan(H, W).chunks * kH32Sums * sizeof(double);
-  return cdn::round256(std::max(tail, dw));
+  return cdn::round256(std::max(tail, dw_part_bytes(N, C, H, W)));
 }
 
 }  // namespace
@@ -512,30 +396,10 @@ extern "C" int cdn_codenet_head_fp32_bn_stats(const float *y, float *running_mea
                                               int64_t C, int64_t H, int64_t W, int training, double eps, double momentum,
                                               void *workspace, size_t workspace_bytes, void *stream) {
   CDN_REQUIRE(y && mean && var && invstd, CDN_ERR_ARG, "null pointer");
-  if (int rc = head32_check_shape(N, C, H, W)) return rc;
-  CDN_REQUIRE(eps >= 0.0, CDN_ERR_ARG, "eps must not be negative");
-  hipStream_t st = cdn::as_stream(stream);
-  const unsigned cgrid = (unsigned)cdn::ceil_div(C, 64);
-  if (!training) {
-    CDN_REQUIRE(running_mean && running_var, CDN_ERR_ARG, "eval mode needs the running statistics");
-    bn_eval_stats_kernel<<<cgrid, 64, 0, st>>>(running_mean, running_var, mean, var, invstd, (int)C, (float)eps);
-    return cdn::check_launch("codenet head fp32 statistics");
-  }
-  CDN_REQUIRE(N * H * W > 1, CDN_ERR_ARG, "batch statistics need more than one value per channel");
-  CDN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), CDN_ERR_ARG, "one running buffer without the other");
-  CDN_REQUIRE(momentum >= 0.0 && momentum <= 1.0, CDN_ERR_ARG, "momentum must lie in [0, 1]");
-  CDN_REQUIRE(workspace, CDN_ERR_ARG, "null workspace");
-  if (int rc = cdn::check_workspace(workspace, workspace_bytes, head32_ws_bytes(N, C, H, W))) return rc;
-  const BnPlan p = bn_plan(N, C, H, W);
-  double *part = static_cast<double *>(workspace);
-  const unsigned grid = (unsigned)(C * p.slabs);
-  if (W % 4 == 0 && cdn::aligned16(y))
-    bn_stats_kernel<true><<<grid, kBnThreads, 0, st>>>(y, part, (int)C, (int)(H * W), p.n, p.slabs);
-  else
-    bn_stats_kernel<false><<<grid, kBnThreads, 0, st>>>(y, part, (int)C, (int)(H * W), p.n, p.slabs);
-  bn_stats_finish_kernel<<<cgrid, 64, 0, st>>>(part, mean, var, invstd, running_mean, running_var,
-                                               reinterpret_cast<long long *>(num_batches_tracked), (int)C, p.slabs, p.n,
-                                               (float)eps, (float)momentum, (float)(1.0 - momentum));
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
+  if (int rc = launch_bn_stats(y, running_mean, running_var, num_batches_tracked, mean, var, invstd, N, C, H, W, training, eps,
+                               momentum, workspace, workspace_bytes, head32_ws_bytes(N, C, H, W), cdn::as_stream(stream)))
+    return rc;
   return cdn::check_launch("codenet head fp32 statistics");
 }
 
@@ -543,8 +407,8 @@ extern "C" int cdn_codenet_head_fp32_dw_forward(const float *y1, const float *me
                                                 const float *gamma1, const float *beta1, const float *w2, float *y2,
                                                 int64_t N, int64_t C, int64_t H, int64_t W, void *stream) {
   CDN_REQUIRE(y1 && mean1 && invstd1 && gamma1 && beta1 && w2 && y2, CDN_ERR_ARG, "null pointer");
-  if (int rc = head32_check_shape(N, C, H, W)) return rc;
-  const H32Plan p = head32_plan(H, W);
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
+  const StripPlan p = strip_plan(H, W);
   const long items = (long)(N * C) * p.strips * p.wq;
   const unsigned grid = (unsigned)cdn::ceil_div(items, 256);
   const bool vec = (W & 3) == 0 && cdn::aligned16(y1) && cdn::aligned16(y2);
@@ -563,7 +427,7 @@ extern "C" int cdn_codenet_head_fp32_tail_forward(const float *y2, const float *
                                                   float *y3, int64_t N, int64_t C, int64_t Co, int64_t H, int64_t W,
                                                   void *stream) {
   CDN_REQUIRE(y2 && mean2 && invstd2 && gamma2 && beta2 && w3 && y3, CDN_ERR_ARG, "null pointer");
-  if (int rc = head32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   CDN_REQUIRE(Co > 0, CDN_ERR_ARG, "non-positive size");
   CDN_REQUIRE(Co <= 4, CDN_ERR_UNSUPPORTED, "1 <= Co <= 4, got %lld", (long long)Co);
   const int64_t HW = H * W;
@@ -598,7 +462,7 @@ extern "C" int cdn_codenet_head_fp32_tail_backward(const float *grad_y3, const f
   CDN_REQUIRE(grad_y3 && y2 && mean2 && invstd2 && gamma2 && beta2 && w3 && g_z2 && grad_gamma2 && grad_beta2 && mb2 && mg2 &&
                   workspace,
               CDN_ERR_ARG, "null pointer");
-  if (int rc = head32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   CDN_REQUIRE(Co > 0, CDN_ERR_ARG, "non-positive size");
   CDN_REQUIRE(Co <= 4, CDN_ERR_UNSUPPORTED, "1 <= Co <= 4, got %lld", (long long)Co);
   if (int rc = cdn::check_workspace(workspace, workspace_bytes, head32_ws_bytes(N, C, H, W))) return rc;
@@ -632,7 +496,7 @@ extern "C" int cdn_codenet_head_fp32_bn_backward1(const float *grad_a, const flo
                                                   int64_t W, void *workspace, size_t workspace_bytes, void *stream) {
   CDN_REQUIRE(grad_a && y && mean && invstd && gamma && beta && g_z && grad_gamma && grad_beta && mb && mg && workspace,
               CDN_ERR_ARG, "null pointer");
-  if (int rc = head32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   CDN_REQUIRE(grad_a != g_z, CDN_ERR_ARG, "g_z must not be grad_a");
   if (int rc = cdn::check_workspace(workspace, workspace_bytes, head32_ws_bytes(N, C, H, W))) return rc;
   const BnPlan p = bn_plan(N, C, H, W);
@@ -645,7 +509,7 @@ extern "C" int cdn_codenet_head_fp32_bn_backward1(const float *grad_a, const flo
   else
     bn_bwd1_kernel<1, false><<<grid, kBnThreads, 0, st>>>(grad_a, y, mean, invstd, gamma, beta, g_z, part, (int)C, (int)H,
                                                           (int)W, p.n, p.slabs);
-  bn_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C, 64), 64, 0, st>>>(part, grad_gamma, grad_beta, mb, mg, (int)C, p.slabs, p.n);
+  launch_bn_bwd_finish(part, grad_gamma, grad_beta, mb, mg, C, p, st);
   return cdn::check_launch("codenet head fp32 BatchNorm backward, first pass");
 }
 
@@ -659,9 +523,9 @@ extern "C" int cdn_codenet_head_fp32_dw_backward(const float *g_z2, const float 
   CDN_REQUIRE(g_z2 && y2 && mean2 && invstd2 && gamma2 && (!training2 || (mb2 && mg2)) && y1 && mean1 && invstd1 && gamma1 &&
                   beta1 && w2 && g_z1 && grad_w2 && grad_gamma1 && grad_beta1 && mb1 && mg1 && workspace,
               CDN_ERR_ARG, "null pointer");
-  if (int rc = head32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   if (int rc = cdn::check_workspace(workspace, workspace_bytes, head32_ws_bytes(N, C, H, W))) return rc;
-  const H32Plan p = head32_plan(H, W);
+  const StripPlan p = strip_plan(H, W);
   const bool vec = (W & 3) == 0 && cdn::aligned16(g_z2) && cdn::aligned16(y2) && cdn::aligned16(y1) && cdn::aligned16(g_z1);
   const unsigned grid = (unsigned)(N * C * p.chunks);
   double *part = static_cast<double *>(workspace);
@@ -676,7 +540,7 @@ extern "C" int cdn_codenet_head_fp32_dw_backward(const float *g_z2, const float 
     if (vec) CDN_HBWD32(false, true); else CDN_HBWD32(false, false);
   }
 #undef CDN_HBWD32
-  head32_dw_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C * kH32Sums, 256), 256, 0, st>>>(
+  dw_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C * kDwSums, 256), 256, 0, st>>>(
       part, grad_w2, grad_gamma1, grad_beta1, mb1, mg1, (int)N, (int)C, p.chunks, (long)(N * H * W));
   return cdn::check_launch("codenet head fp32 depthwise backward");
 }
@@ -686,7 +550,7 @@ extern "C" int cdn_codenet_head_fp32_bn_backward2(const float *g_z, const float 
                                                   int64_t grad_y_image_pitch, int64_t N, int64_t C, int64_t H, int64_t W,
                                                   int training, void *stream) {
   CDN_REQUIRE(g_z && y && mean && invstd && gamma && (!training || (mb && mg)) && grad_y, CDN_ERR_ARG, "null pointer");
-  if (int rc = head32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   CDN_REQUIRE(grad_y_image_pitch >= C * H * W, CDN_ERR_ARG, "image pitch of grad_y below C * H * W");
   CDN_REQUIRE(N * grad_y_image_pitch < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
   const long rows = (long)(N * C * H);

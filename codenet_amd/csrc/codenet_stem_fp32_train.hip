@@ -18,7 +18,7 @@
 //   g_z       pooled: a window's gradient goes to that first maximum; a pixel adds the gradients of the windows it won in
 //             row-major window order from 0.0f (a gather: every element written once), then g_z = z > 0 ? sum : 0.
 //             un-pooled: g_z = z > 0 ? grad_out : 0, formed on load, not stored.
-//   grad_y0   = ((g_z - mb) - xh mg) (gamma invstd) (training) or g_z (gamma invstd) (eval): head32 / bn_bwd2_kernel's
+//   grad_y0   = ((g_z - mb) - xh mg) (gamma invstd) (training) or g_z (gamma invstd) (eval): bn_grad_y, as bn_bwd2_kernel's,
 //             expression, formed on load in the weight-gradient kernel.
 //   grad_W    [24][27] = sum grad_y0[n][c][oy][ox] img[n][ci][oy S + dy - 1][ox S + dx - 1] (zero outside the image)
 // ---- the sums ---------------------------------------------------------------------------------------------------------------
@@ -235,7 +235,7 @@ stem32_pool_bwd_kernel(const float *__restrict__ g, const float *__restrict__ y0
         }
     }
   }
-  block_sums_store_f64(t1, t2, red, part);
+  cdn::block_sums_store({t1, t2}, red, part);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -256,14 +256,11 @@ stem32_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ y0, c
   const long start = (long)(blockIdx.x % chunks) * 256 * per_thread;
   const int HW = Ho * Wo;
   BnCh p[kS32Group];
-  float k[kS32Group], b[kS32Group], a[kS32Group];
+  BnBwd2 q[kS32Group];
 #pragma unroll
   for (int e = 0; e < kS32Group; ++e) {
-    const int c = grp * kS32Group + e;
-    p[e] = load_ch(mean, invstd, gamma, beta, c);
-    k[e] = p[e].gamma * p[e].invstd;
-    b[e] = SUB ? mb[c] : 0.0f;
-    a[e] = SUB ? mg[c] : 0.0f;
+    p[e] = load_ch(mean, invstd, gamma, beta, grp * kS32Group + e);
+    q[e] = load_bwd2<SUB>(mean, invstd, gamma, mb, mg, grp * kS32Group + e);
   }
   float sums[kS32Part];      // [kS32Group][kS32Sums]
 #pragma unroll
@@ -278,19 +275,10 @@ stem32_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ y0, c
       const long o = ((long)n * kS32Co + grp * kS32Group) * HW + pos;
 #pragma unroll
       for (int e = 0; e < kS32Group; ++e) {
-        const float gv = g[o + (long)e * HW];
+        const float gv = g[o + (long)e * HW], yv = y0[o + (long)e * HW];
         float xh;
-        const float z = bn_z(y0[o + (long)e * HW], p[e], xh);
-        const float gzv = MASKED ? gv : (z > 0.0f ? gv : 0.0f);
-        float gy;
-        if (SUB) {
-          const float t1 = gzv - b[e];
-          const float t2 = xh * a[e];
-          const float t3 = t1 - t2;
-          gy = t3 * k[e];
-        } else {
-          gy = gzv * k[e];
-        }
+        const float z = bn_z(yv, p[e], xh);
+        const float gy = bn_grad_y<SUB>(MASKED ? gv : (z > 0.0f ? gv : 0.0f), yv, q[e]);
 #pragma unroll
         for (int t = 0; t < kS32Taps; ++t) sums[e * kS32Sums + t] = fmaf(gy, v[t], sums[e * kS32Sums + t]);
       }
@@ -301,16 +289,12 @@ stem32_wgrad_kernel(const float *__restrict__ g, const float *__restrict__ y0, c
 
 int stem32_pool_hw(int64_t v) { return (int)((v - 1) / 2 + 1); }
 
-// what bn_check_shape(N, C, H, W, 1) accepts, without an error message: the size queries answer 0 otherwise
-bool stem32_shape_ok(int64_t N, int64_t C, int64_t H, int64_t W) {
-  return N > 0 && C > 0 && H > 0 && W > 0 && N * C * H * W < (1ll << 31) &&
-         C * cdn::ceil_div(N * H * W, kBnSlab) < (1ll << 31);
-}
-
 }  // namespace
 
 extern "C" size_t cdn_codenet_stem_fp32_workspace_bytes(int64_t N, int64_t C, int64_t H, int64_t W) {
-  if (!stem32_shape_ok(N, C, H, W)) return 0;
+  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || N * C * H * W >= (1ll << 31) ||
+      C * cdn::ceil_div(N * H * W, kBnSlab) >= (1ll << 31))
+    return 0;      // what bn_check_shape refuses
   return bn_plan(N, C, H, W).part_bytes;
 }
 
@@ -356,7 +340,7 @@ extern "C" int cdn_codenet_stem_fp32_pool_backward(const float *g, const float *
   else
     stem32_pool_bwd_kernel<false><<<grid, kBnThreads, 0, st>>>(g, y0, mean, invstd, gamma, beta, g_z, part, (int)C, (int)H,
                                                                (int)W, Hp, Wp, p.n, p.slabs);
-  bn_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C, 64), 64, 0, st>>>(part, grad_gamma, grad_beta, mb, mg, (int)C, p.slabs, p.n);
+  launch_bn_bwd_finish(part, grad_gamma, grad_beta, mb, mg, C, p, st);
   return cdn::check_launch("codenet stem fp32 pool backward");
 }
 
@@ -379,7 +363,7 @@ extern "C" int cdn_codenet_stem_fp32_bn_relu_backward_sums(const float *g, const
   else
     bn_bwd1_kernel<1, false, false><<<grid, kBnThreads, 0, st>>>(g, y0, mean, invstd, gamma, beta, nullptr, part, (int)C,
                                                                  (int)H, (int)W, p.n, p.slabs);
-  bn_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C, 64), 64, 0, st>>>(part, grad_gamma, grad_beta, mb, mg, (int)C, p.slabs, p.n);
+  launch_bn_bwd_finish(part, grad_gamma, grad_beta, mb, mg, C, p, st);
   return cdn::check_launch("codenet stem fp32 BatchNorm + ReLU backward sums");
 }
 

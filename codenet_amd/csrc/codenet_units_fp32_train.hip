@@ -37,53 +37,12 @@
 
 namespace {
 
-constexpr int kU32Rows = 8;       // rows of a thread's strip
-constexpr int kU32Sums = 11;      // per-plane sums of the depthwise backward: nine taps of grad_w, T1, T2
-
-// K float64 sums of a workgroup -> part[blockIdx.x][K]; every thread calls it.  red: K doubles of LDS per wave.
-template <int K>
-__device__ __forceinline__ void unit32_block_sums_store(const double (&sums)[K], double *red, double *__restrict__ part) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double v = sums[k];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (lane == 0) red[wave * K + k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double s = red[threadIdx.x];
-    for (int i = 1; i < nw; ++i) s += red[i * K + threadIdx.x];
-    part[(long)blockIdx.x * K + threadIdx.x] = s;
-  }
-}
-
 __device__ __forceinline__ BnCh unit32_ch(bool bn, const float *__restrict__ mean, const float *__restrict__ invstd,
                                           const float *__restrict__ gamma, const float *__restrict__ beta, int c) {
   if (bn) return load_ch(mean, invstd, gamma, beta, c);
   BnCh p;
   p.mean = p.invstd = p.gamma = p.beta = 0.0f;
   return p;
-}
-
-// One window row (NC columns from xa - 1) of the depthwise input.  BN: a = relu(bn_z(v)) inside the plane, literal zeros
-// outside; !BN: the stored values as they are (zeros outside).
-template <int NC, bool BN, bool VEC>
-__device__ __forceinline__ void load_in(const float *__restrict__ plane, int y, int H, int W, int xa, const BnCh &p,
-                                        float (&a)[NC]) {
-  float v[NC];
-  const unsigned ok = cdn::load_cols<NC, 1, VEC>(plane, y, H, W, xa, v);
-#pragma unroll
-  for (int j = 0; j < NC; ++j) {
-    if (BN) {
-      float xh;
-      const float z = bn_z(v[j], p, xh);
-      a[j] = ((ok >> j) & 1u) ? cdn::relu_keep_nan(z) : 0.0f;
-    } else {
-      a[j] = v[j];
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -105,7 +64,7 @@ unit32_dw_fwd_kernel(const float *__restrict__ in, long in_pitch, const float *_
   const long plane = t / strips;
   const int c = (int)(plane % C);
   const long n = plane / C;
-  const int x0 = q * 4, ya = strip * kU32Rows, yb = min(Ho, ya + kU32Rows);
+  const int x0 = q * 4, ya = strip * kStripRows, yb = min(Ho, ya + kStripRows);
   const float *src = in + n * in_pitch + (long)c * H * W;
   float *dst = out + plane * Ho * Wo;
   const BnCh p = unit32_ch(BN, mean, invstd, gamma, beta, c);
@@ -113,14 +72,14 @@ unit32_dw_fwd_kernel(const float *__restrict__ in, long in_pitch, const float *_
 #pragma unroll
   for (int k = 0; k < 9; ++k) w[k] = w9[c * 9 + k];
   float a[3][NC];
-  load_in<NC, BN, VIN>(src, ya * S - 1, H, W, x0 * S, p, a[0]);
-  if (S == 1) load_in<NC, BN, VIN>(src, ya, H, W, x0, p, a[1]);
+  load_win<NC, BN, VIN>(src, ya * S - 1, H, W, x0 * S, p, a[0]);
+  if (S == 1) load_win<NC, BN, VIN>(src, ya, H, W, x0, p, a[1]);
   for (int y = ya; y < yb; ++y) {
     if (S == 1) {
-      load_in<NC, BN, VIN>(src, y + 1, H, W, x0, p, a[2]);
+      load_win<NC, BN, VIN>(src, y + 1, H, W, x0, p, a[2]);
     } else {
-      load_in<NC, BN, VIN>(src, 2 * y, H, W, 2 * x0, p, a[1]);
-      load_in<NC, BN, VIN>(src, 2 * y + 1, H, W, 2 * x0, p, a[2]);
+      load_win<NC, BN, VIN>(src, 2 * y, H, W, 2 * x0, p, a[1]);
+      load_win<NC, BN, VIN>(src, 2 * y + 1, H, W, 2 * x0, p, a[2]);
     }
     float o[4];
 #pragma unroll
@@ -276,7 +235,7 @@ unit32_bwd1_kernel(const float *__restrict__ g, const float *__restrict__ y, con
         }
     }
   }
-  block_sums_store_f64(t1, t2, red, part);
+  cdn::block_sums_store({t1, t2}, red, part);
 }
 
 // The terms of one row of a thread's strip: the four pixels x0 .. x0 + 3 of an input row.  gK: the window row of grad_y
@@ -286,7 +245,7 @@ unit32_bwd1_kernel(const float *__restrict__ g, const float *__restrict__ y, con
 template <int S, bool D0, bool D1, bool D2, int NG>
 __device__ __forceinline__ void unit32_bwd_row(const float (&g0)[NG], const float (&g1)[NG], const float (&g2)[NG],
                                                const float (&w)[9], const float (&a)[4], int x0, int W,
-                                               double (&sums)[kU32Sums], float (&ga)[4]) {
+                                               double (&sums)[kDwSums], float (&ga)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     float acc = 0.0f;
@@ -326,28 +285,26 @@ unit32_dw_bwd_kernel(const float *__restrict__ gz, const float *__restrict__ y, 
                      const float *__restrict__ beta1, const float *__restrict__ w9, float *gin, long gin_pitch, int acc,
                      double *__restrict__ part, int C, int H, int W, int Ho, int Wo, int wq, int strips, int chunks) {
   constexpr int NG = S == 1 ? 6 : 3;
-  __shared__ double red[4 * kU32Sums];
+  __shared__ double red[4 * kDwSums];
   const int chunk = (int)(blockIdx.x % chunks);
   const long plane = blockIdx.x / chunks;
   const int c = (int)(plane % C);
   const long n = plane / C;
   const int item = chunk * (int)blockDim.x + (int)threadIdx.x;
-  double sums[kU32Sums];
+  double sums[kDwSums];
 #pragma unroll
-  for (int k = 0; k < kU32Sums; ++k) sums[k] = 0.0;
+  for (int k = 0; k < kDwSums; ++k) sums[k] = 0.0;
   if (item < wq * strips) {
-    const int x0 = (item % wq) * 4, ya = (item / wq) * kU32Rows, yb = min(H, ya + kU32Rows);
+    const int x0 = (item % wq) * 4, ya = (item / wq) * kStripRows, yb = min(H, ya + kStripRows);
     const float *gsrc = gz + plane * Ho * Wo, *ysrc = y + plane * Ho * Wo;
     const float *isrc = in + n * in_pitch + (long)c * H * W;
     float *dst = gin ? gin + n * gin_pitch + (long)c * H * W : nullptr;
     const BnCh p1 = unit32_ch(BN, mean1, invstd1, gamma1, beta1, c);
-    const float mu2 = mean2[c], is2 = invstd2[c];
-    const float k2 = gamma2[c] * is2;
-    const float b2 = SUB ? mb2[c] : 0.0f, a2 = SUB ? mg2[c] : 0.0f;
+    const BnBwd2 q2 = load_bwd2<SUB>(mean2, invstd2, gamma2, mb2, mg2, c);
     float w[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) w[k] = w9[c * 9 + k];
-    // one window row of grad_y (head32_bn_bwd2_kernel's expression), zeros outside the plane
+    // one window row of grad_y (bn_grad_y), zeros outside the plane
     auto load_g = [&](int yo, float (&gr)[NG]) {
       float gv[NG], yv[NG];
       unsigned ok = 0u;
@@ -365,20 +322,7 @@ unit32_dw_bwd_kernel(const float *__restrict__ gz, const float *__restrict__ y, 
         }
       }
 #pragma unroll
-      for (int j = 0; j < NG; ++j) {
-        float o;
-        if (SUB) {
-          const float d = yv[j] - mu2;
-          const float xh = d * is2;
-          const float t1 = gv[j] - b2;
-          const float t2 = xh * a2;
-          const float t3 = t1 - t2;
-          o = t3 * k2;
-        } else {
-          o = gv[j] * k2;
-        }
-        gr[j] = ((ok >> j) & 1u) ? o : 0.0f;
-      }
+      for (int j = 0; j < NG; ++j) gr[j] = ((ok >> j) & 1u) ? bn_grad_y<SUB>(gv[j], SUB ? yv[j] : 0.0f, q2) : 0.0f;
     };
     // the thread's own four pixels of input row Y: a, the mask z > 0 and xh (BN) or the stored values
     float a[4], xh[4], ga[4];
@@ -470,53 +414,7 @@ unit32_dw_bwd_kernel(const float *__restrict__ gz, const float *__restrict__ y, 
       }
     }
   }
-  unit32_block_sums_store<kU32Sums>(sums, red, part);
-}
-
-// one thread per (channel, sum): the partials [N][C][chunks][11] added in index order (images, then chunks); leaves
-// grad_w [C][9] and (grad_gamma != NULL) grad_gamma, grad_beta and the two means of BatchNorm1's second pass
-__global__ void __launch_bounds__(256)
-unit32_dw_bwd_finish_kernel(const double *__restrict__ part, float *__restrict__ grad_w, float *__restrict__ grad_gamma,
-                            float *__restrict__ grad_beta, float *__restrict__ mb, float *__restrict__ mg, int N, int C,
-                            int chunks, long n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * kU32Sums) return;
-  const int c = i / kU32Sums, k = i % kU32Sums;
-  if (k >= 9 && !grad_gamma) return;
-  double s = 0.0;
-  for (int img = 0; img < N; ++img)
-    for (int h = 0; h < chunks; ++h) s = s + part[(((long)img * C + c) * chunks + h) * kU32Sums + k];
-  if (k < 9) {
-    grad_w[c * 9 + k] = (float)s;
-  } else if (k == 9) {
-    grad_beta[c] = (float)s;
-    mb[c] = (float)(s / (double)n);
-  } else {
-    grad_gamma[c] = (float)s;
-    mg[c] = (float)(s / (double)n);
-  }
-}
-
-struct U32Plan {
-  int wq, strips, threads, chunks;
-};
-U32Plan unit32_plan(int64_t H, int64_t W) {
-  U32Plan p;
-  p.wq = (int)cdn::ceil_div(W, 4);
-  p.strips = (int)cdn::ceil_div(H, kU32Rows);
-  const long items = (long)p.wq * p.strips;
-  p.threads = (int)std::min<long>(256, cdn::ceil_div(items, 64) * 64);
-  p.chunks = (int)cdn::ceil_div(items, p.threads);
-  return p;
-}
-
-// [N][C][H][W] tensors of a unit: positive sizes, 32-bit indexing, grids below 2^31
-int unit32_check_shape(int64_t N, int64_t C, int64_t H, int64_t W) {
-  CDN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, CDN_ERR_ARG, "non-positive size");
-  CDN_REQUIRE(N * C * H * W < (1ll << 31), CDN_ERR_UNSUPPORTED, "shape too large");
-  CDN_REQUIRE(C * cdn::ceil_div(N * H * W, kBnSlab) < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
-  CDN_REQUIRE(N * C * unit32_plan(H, W).chunks < (1ll << 31), CDN_ERR_UNSUPPORTED, "too many workgroups");
-  return CDN_OK;
+  cdn::block_sums_store(sums, red, part);
 }
 
 // a channel slice [N][C][H][W] of a wider tensor behind an image pitch
@@ -529,8 +427,7 @@ int unit32_check_pitch(int64_t pitch, int64_t N, int64_t C, int64_t H, int64_t W
 size_t unit32_ws_bytes(int64_t N, int64_t C, int64_t H, int64_t W) {
   const size_t slabs = (size_t)cdn::ceil_div(N * H * W, kBnSlab);
   const size_t bn = (size_t)C * slabs * 2 * sizeof(double);
-  const size_t dw = (size_t)N * (size_t)C * (size_t)unit32_plan(H, W).chunks * kU32Sums * sizeof(double);
-  return cdn::round256(std::max(bn, dw));
+  return cdn::round256(std::max(bn, dw_part_bytes(N, C, H, W)));
 }
 
 bool unit32_stride_ok(int stride) { return stride == 1 || stride == 2; }
@@ -551,10 +448,10 @@ extern "C" int cdn_codenet_unit_fp32_dw_forward(const float *in, int64_t in_imag
   CDN_REQUIRE(bn ? (invstd && gamma && beta) : (!invstd && !gamma && !beta), CDN_ERR_ARG,
               "mean, invstd, gamma, beta: all four or none");
   CDN_REQUIRE(unit32_stride_ok(stride), CDN_ERR_ARG, "stride must be 1 or 2, got %d", stride);
-  if (int rc = unit32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   if (int rc = unit32_check_pitch(in_image_pitch, N, C, H, W, "in")) return rc;
   const int64_t Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  const U32Plan p = unit32_plan(Ho, Wo);
+  const StripPlan p = strip_plan(Ho, Wo);
   const long items = (long)(N * C) * p.strips * p.wq;
   const unsigned grid = (unsigned)cdn::ceil_div(items, 256);
   const bool vin = (W & 3) == 0 && (in_image_pitch & 3) == 0 && cdn::aligned16(in);
@@ -582,7 +479,7 @@ extern "C" int cdn_codenet_unit_fp32_bn_forward(const float *y, const float *mea
                                                 const float *beta, float *z, int64_t N, int64_t C, int64_t H, int64_t W,
                                                 void *stream) {
   CDN_REQUIRE(y && mean && invstd && gamma && beta && z, CDN_ERR_ARG, "null pointer");
-  if (int rc = unit32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   const int64_t HW = H * W;
   const unsigned grid = rows_grid((long)(N * C), HW);
   hipStream_t st = cdn::as_stream(stream);
@@ -602,7 +499,7 @@ extern "C" int cdn_codenet_unit_fp32_join_forward(const float *y, const float *m
   CDN_REQUIRE(y && mean && invstd && gamma && beta && out, CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(slot == 0 || slot == 1, CDN_ERR_ARG, "slot must be 0 or 1, got %d", slot);
   CDN_REQUIRE(!x1 || slot == 1, CDN_ERR_ARG, "the pass-through half goes with slot 1");
-  if (int rc = unit32_check_shape(N, 2 * h, H, W)) return rc;
+  if (int rc = train32_check_shape(N, 2 * h, H, W)) return rc;
   if (x1)
     if (int rc = unit32_check_pitch(x1_image_pitch, N, h, H, W, "x1")) return rc;
   const int64_t HW = H * W;
@@ -629,7 +526,7 @@ extern "C" int cdn_codenet_unit_fp32_join_backward(const float *grad_out, const 
               CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(slot == 0 || slot == 1, CDN_ERR_ARG, "slot must be 0 or 1, got %d", slot);
   CDN_REQUIRE(!grad_x1 || slot == 1, CDN_ERR_ARG, "the pass-through half goes with slot 1");
-  if (int rc = unit32_check_shape(N, 2 * h, H, W)) return rc;
+  if (int rc = train32_check_shape(N, 2 * h, H, W)) return rc;
   if (grad_x1)
     if (int rc = unit32_check_pitch(grad_x1_image_pitch, N, h, H, W, "grad_x1")) return rc;
   if (int rc = cdn::check_workspace(workspace, workspace_bytes, unit32_ws_bytes(N, h, H, W))) return rc;
@@ -646,7 +543,7 @@ extern "C" int cdn_codenet_unit_fp32_join_backward(const float *grad_out, const 
   else
     unit32_bwd1_kernel<true, false><<<grid, kBnThreads, 0, st>>>(grad_out, y, mean, invstd, gamma, beta, g_z, slot, grad_x1,
                                                                  (long)grad_x1_image_pitch, part, (int)h, (int)HW, p.n, p.slabs);
-  bn_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(h, 64), 64, 0, st>>>(part, grad_gamma, grad_beta, mb, mg, (int)h, p.slabs, p.n);
+  launch_bn_bwd_finish(part, grad_gamma, grad_beta, mb, mg, h, p, st);
   return cdn::check_launch("codenet unit fp32 join backward");
 }
 
@@ -655,7 +552,7 @@ extern "C" int cdn_codenet_unit_fp32_bn_backward_sums(const float *grad_z, const
                                                       float *mg, int64_t N, int64_t C, int64_t H, int64_t W, void *workspace,
                                                       size_t workspace_bytes, void *stream) {
   CDN_REQUIRE(grad_z && y && mean && invstd && grad_gamma && grad_beta && mb && mg && workspace, CDN_ERR_ARG, "null pointer");
-  if (int rc = unit32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   if (int rc = cdn::check_workspace(workspace, workspace_bytes, unit32_ws_bytes(N, C, H, W))) return rc;
   const BnPlan p = bn_plan(N, C, H, W);
   double *part = static_cast<double *>(workspace);
@@ -668,7 +565,7 @@ extern "C" int cdn_codenet_unit_fp32_bn_backward_sums(const float *grad_z, const
   else
     unit32_bwd1_kernel<false, false><<<grid, kBnThreads, 0, st>>>(grad_z, y, mean, invstd, nullptr, nullptr, nullptr, 0, nullptr,
                                                                   0, part, (int)C, (int)HW, p.n, p.slabs);
-  bn_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C, 64), 64, 0, st>>>(part, grad_gamma, grad_beta, mb, mg, (int)C, p.slabs, p.n);
+  launch_bn_bwd_finish(part, grad_gamma, grad_beta, mb, mg, C, p, st);
   return cdn::check_launch("codenet unit fp32 BatchNorm backward sums");
 }
 
@@ -690,13 +587,13 @@ extern "C" int cdn_codenet_unit_fp32_dw_backward(const float *grad_z, const floa
     CDN_REQUIRE(!invstd1 && !gamma1 && !beta1 && !grad_gamma1 && !grad_beta1 && !mb1 && !mg1, CDN_ERR_ARG,
                 "no BatchNorm1: its operands and results must all be NULL");
   CDN_REQUIRE(unit32_stride_ok(stride), CDN_ERR_ARG, "stride must be 1 or 2, got %d", stride);
-  if (int rc = unit32_check_shape(N, C, H, W)) return rc;
+  if (int rc = train32_check_shape(N, C, H, W)) return rc;
   if (int rc = unit32_check_pitch(in_image_pitch, N, C, H, W, "in")) return rc;
   if (grad_in)
     if (int rc = unit32_check_pitch(grad_in_image_pitch, N, C, H, W, "grad_in")) return rc;
   if (int rc = cdn::check_workspace(workspace, workspace_bytes, unit32_ws_bytes(N, C, H, W))) return rc;
   const int64_t Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  const U32Plan p = unit32_plan(H, W);
+  const StripPlan p = strip_plan(H, W);
   const bool vi = (W & 3) == 0 && (in_image_pitch & 3) == 0 && cdn::aligned16(in) &&
                   (!grad_in || ((grad_in_image_pitch & 3) == 0 && cdn::aligned16(grad_in)));
   const bool vo = stride == 1 && (Wo & 3) == 0 && cdn::aligned16(grad_z) && cdn::aligned16(y);
@@ -727,7 +624,7 @@ extern "C" int cdn_codenet_unit_fp32_dw_backward(const float *grad_z, const floa
 #undef CDN_U32BWD_M
 #undef CDN_U32BWD_V
 #undef CDN_U32BWD
-  unit32_dw_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C * kU32Sums, 256), 256, 0, st>>>(
+  dw_bwd_finish_kernel<<<(unsigned)cdn::ceil_div(C * kDwSums, 256), 256, 0, st>>>(
       part, grad_w, grad_gamma1, grad_beta1, mb1, mg1, (int)N, (int)C, p.chunks, (long)(N * H * W));
   return cdn::check_launch("codenet unit fp32 depthwise backward");
 }

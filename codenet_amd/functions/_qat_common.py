@@ -1,6 +1,7 @@
 """What the native functions of the QAT step share (codenet_heads.py, codenet_units.py, codenet_stem.py): the QuantAct
 update around a launch, the multi-tensor weight fold, and the gates that decide between the kernels and the module path.
-A gate returns None or the reason -- a string -- why the module path is taken."""
+A gate returns None or the reason -- a string -- why the module path is taken.  The fp32 training step (_fp32_common.py)
+takes the structural predicates and the input gate from here."""
 import torch
 import torch.nn as nn
 

@@ -15,7 +15,7 @@ from torch.autograd.function import once_differentiable
 from .. import _native as N_
 from .. import ops
 from . import codenet_stage as CS
-from ._qat_common import _hook_reason
+from ._fp32_common import _bn_settings_reason, _hook_reason, _one_value_error, _placement_reason, bn_relu_up
 
 # A/B switch (tools/fp32_block_bench.py): False restores the module path (``seq(x)``) for the fp32 blocks
 NATIVE_FP32_BLOCKS = True
@@ -33,9 +33,7 @@ class BnReluUpsample(Function):
         y = y.contiguous()
         training = bool(bn.training)
         ws = CS._workspace(N_.lib().cdn_codenet_bn_workspace_bytes(*y.shape), y.device) if training else None
-        out, mean, var, invstd = ops.bn_relu_up_forward(
-            y, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None, bn.eps,
-            bn.momentum, up, training, ws=ws)
+        out, mean, var, invstd = bn_relu_up(y, gamma, beta, bn, up, ws=ws)
         ctx.up, ctx.training = int(up), training
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(y, gamma, beta, mean, invstd)
@@ -81,12 +79,9 @@ def native_reason(seq, x):
             return "%s: the stage is not the co-designed depthwise form" % what
         if type(bn) is not nn.BatchNorm2d or not isinstance(relu, nn.ReLU) or not _is_up2(up):
             return "%s: a mixed sequence (not BatchNorm2d, ReLU, Upsample(x2, nearest))" % what
-        if not bn.affine:
-            return "%s: BatchNorm2d(affine=False)" % what
-        if not bn.track_running_stats or bn.running_mean is None:
-            return "%s: BatchNorm2d(track_running_stats=False)" % what
-        if bn.momentum is None:
-            return "%s: BatchNorm2d(momentum=None), the cumulative average" % what
+        why = _bn_settings_reason(bn, what)
+        if why is not None:
+            return why
         if bn.num_features != st.out_channels:
             return "%s: the BatchNorm2d has %d features, the stage %d channels" % (what, bn.num_features, st.out_channels)
         for m, name in ((st, "stage"), (bn, "BatchNorm2d"), (relu, "ReLU"), (up, "Upsample")):
@@ -109,12 +104,12 @@ def native_reason(seq, x):
         H, W = 2 * H, 2 * W
     for i in range(0, len(mods), 4):
         st, bn = mods[i], mods[i + 1]
-        for t in list(st.parameters()) + list(bn.parameters()) + list(bn.buffers()):
-            if t.device != x.device or (t.is_floating_point() and t.dtype != torch.float32):
-                return "block %d: a parameter or buffer is not a float32 tensor on x's device" % (i // 4)
-    if not (x.requires_grad or any(p.requires_grad for m in mods for p in m.parameters())):
-        return "nothing to differentiate (the stages take their inference kernels)"
-    return None
+        why = _placement_reason(x, list(st.parameters()) + list(bn.parameters()), bn.buffers(), "block %d: " % (i // 4),
+                                nothing=None)
+        if why is not None:
+            return why
+    return _placement_reason(x, [p for m in mods for p in m.parameters()], (),
+                             nothing="nothing to differentiate (the stages take their inference kernels)")
 
 
 def forward_fp32_blocks(seq, x, keep=None):
@@ -130,8 +125,7 @@ def forward_fp32_blocks(seq, x, keep=None):
         pw = st.conv_channel if st.in_channels != st.out_channels else None
         Nb, H, W = x.shape[0], x.shape[2] * (2 if x_up else 1), x.shape[3] * (2 if x_up else 1)      # the stage's plane
         if bn.training and Nb * H * W == 1:
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s"
-                             % ((Nb, st.out_channels, H, W),))
+            raise _one_value_error((Nb, st.out_channels, H, W))
         y = CS.codenet_stage(x, st.conv_scale.weight, st.conv_scale.bias, st.conv.weight,
                              pw.weight if pw is not None else None, pw.bias if pw is not None else None,
                              st.conv_bound.min_val, st.conv_bound.max_val, x_up=x_up)

@@ -35,7 +35,8 @@ from torch.autograd.function import once_differentiable
 from .. import _native as N_
 from .. import ops
 from . import codenet_stage as CS
-from ._qat_common import _hook_reason, _input_reason, _is_1x1, _is_dw
+from ._fp32_common import (_bn_reason, _hook_reason, _input_reason, _is_1x1, _is_dw, _one_value_error, _placement_reason,
+                           bn_backward2, bn_relu_up, bn_stats)
 
 # A/B switch (tools/heads_fp32_bench.py): the fp32 heads of a training step on the kernels above (True) or module by module
 # through the framework's autograd (False)
@@ -46,21 +47,6 @@ _p = CS._p
 
 def _ws(shape, device):
     return CS._workspace(N_.lib().cdn_codenet_head_fp32_workspace_bytes(*shape), device)
-
-
-def bn_stats(y, bn):
-    """(mean, var, invstd), the rows of one [3, C] tensor, of y for the BatchNorm2d `bn`: batch statistics with the buffers
-    advanced in place (bn.training) or the running statistics (nothing written).  cdn_codenet_head_fp32_bn_stats."""
-    Nb, C, H, W = y.shape
-    training = bool(bn.training)
-    stats = y.new_empty(3, C)
-    ws = _ws(y.shape, y.device) if training else None
-    rc = N_.lib().cdn_codenet_head_fp32_bn_stats(
-        _p(y), _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked) if training else None, _p(stats[0]),
-        _p(stats[1]), _p(stats[2]), Nb, C, H, W, int(training), float(bn.eps), float(bn.momentum), _p(ws),
-        ws.numel() * 4 if ws is not None else 0, ops._stream(y))
-    N_.check(rc, "cdn_codenet_head_fp32_bn_stats")
-    return stats
 
 
 def dw_forward(y1, st1, gamma1, beta1, w2):
@@ -126,15 +112,6 @@ def dw_backward(gz2, y2, st2, gamma2, means2, training2, y1, st1, gamma1, beta1,
     return gz1, gw2, gg, gb, means
 
 
-def bn_backward2(gz, y, st, gamma, means, training, out, slot, pitch):
-    """grad_y of BatchNorm's second pass into channels [slot * C, (slot + 1) * C) of `out` [N, pitch / (H W), H, W]."""
-    Nb, C, H, W = y.shape
-    rc = N_.lib().cdn_codenet_head_fp32_bn_backward2(_p(gz), _p(y), _p(st[0]), _p(st[2]), _p(gamma), _p(means[0]),
-                                                     _p(means[1]), out.data_ptr() + 4 * slot * C * H * W, pitch, Nb, C, H, W,
-                                                     int(bool(training)), ops._stream(y))
-    N_.check(rc, "cdn_codenet_head_fp32_bn_backward2")
-
-
 class CodenetHeadsFp32Function(Function):
     """(y3 of every head) = heads(x).  meta: one (name, bn1, bn2) per head; flat: W1, gamma1, beta1, W2, gamma2, beta2, W3,
     b3 per head.  The BatchNorm buffers are updated in place by the forward, as the module path does.  keep (a dict or
@@ -158,10 +135,7 @@ class CodenetHeadsFp32Function(Function):
                 a2 = y2             # (a placeholder: a2 is never stored)
                 y3 = tail_forward(y2, st2, g2, b2, w3, b3)
             else:
-                training2 = bool(bn2.training)
-                a2, *st2 = ops.bn_relu_up_forward(
-                    y2, g2, b2, bn2.running_mean, bn2.running_var, bn2.num_batches_tracked if training2 else None, bn2.eps,
-                    bn2.momentum, 1, training2)
+                a2, *st2 = bn_relu_up(y2, g2, b2, bn2)
                 y3 = ops.codenet_pointwise(a2, w3, b3)
             if keep is not None:
                 keep[name] = {"y1": y1, "y2": y2, "bn1": tuple(st1), "bn2": tuple(st2)}
@@ -221,20 +195,6 @@ class CodenetHeadsFp32Function(Function):
         return tuple(grads)
 
 
-def _bn_reason(bn, C, what):
-    if type(bn) is not nn.BatchNorm2d:
-        return "%s is a %s, not a BatchNorm2d" % (what, type(bn).__name__)
-    if not bn.affine:
-        return "%s: BatchNorm2d(affine=False)" % what
-    if not bn.track_running_stats or bn.running_mean is None:
-        return "%s: BatchNorm2d(track_running_stats=False)" % what
-    if bn.momentum is None:
-        return "%s: BatchNorm2d(momentum=None), the cumulative average" % what
-    if bn.num_features != C:
-        return "%s has %d features, the convolution in front of it %d channels" % (what, bn.num_features, C)
-    return None
-
-
 def _head_reason(name, mod):
     what = "head '%s'" % name
     if not isinstance(mod, nn.Sequential) or len(mod) != 7:
@@ -286,12 +246,10 @@ def native_reason(heads, x):
     for name, mod in heads.items():
         if mod[0].in_channels != x.shape[1]:
             return "head '%s' expects %d input channels, x has %d" % (name, mod[0].in_channels, x.shape[1])
-        for t in list(mod.parameters()) + list(mod.buffers()):
-            if t.device != x.device or (t.is_floating_point() and t.dtype != torch.float32):
-                return "head '%s': a parameter or buffer is not a float32 tensor on x's device" % name
-    if not (x.requires_grad or any(p.requires_grad for m in heads.values() for p in m.parameters())):
-        return "nothing to differentiate"
-    return None
+        why = _placement_reason(x, mod.parameters(), mod.buffers(), "head '%s': " % name, nothing=None)
+        if why is not None:
+            return why
+    return _placement_reason(x, [p for m in heads.values() for p in m.parameters()], ())      # (placed: it asks for grad)
 
 
 def forward_fp32_heads(heads, x, keep=None):
@@ -301,8 +259,7 @@ def forward_fp32_heads(heads, x, keep=None):
     mods = [heads[h] for h in names]
     Nb, _, H, W = x.shape
     if Nb * H * W == 1 and any(m[i].training for m in mods for i in (1, 4)):
-        raise ValueError("Expected more than 1 value per channel when training, got input size %s"
-                         % ((Nb, mods[0][0].out_channels, H, W),))
+        raise _one_value_error((Nb, mods[0][0].out_channels, H, W))
     meta = tuple((h, m[1], m[4]) for h, m in zip(names, mods))
     flat = []
     for m in mods:

@@ -30,18 +30,14 @@ from torch.autograd.function import once_differentiable
 from .. import _native as N_
 from .. import ops
 from . import codenet_stage as CS
-from ._qat_common import _hook_reason, _input_reason
-from .codenet_heads_fp32 import _bn_reason, bn_stats
+from ._fp32_common import (_bn_reason, _hook_reason, _input_reason, _one_value_error, _out_hw, _placement_reason, bn_relu_up,
+                           bn_stats)
 
 # A/B switch (tools/stem_fp32_bench.py): the fp32 stem of a training step on the kernels above (True) or module by module
 # through the framework's autograd (False)
 NATIVE_FP32_STEM = True
 
 _p = CS._p
-
-
-def _out_hw(H, W, stride):
-    return (H - 1) // stride + 1, (W - 1) // stride + 1
 
 
 def _conv_forward(x, w, stride):
@@ -118,8 +114,7 @@ class CodenetStemFp32Function(Function):
             st = bn_stats(y0, bn)
             out = _pool_forward(y0, st, gamma, beta)
         else:
-            out, *st = ops.bn_relu_up_forward(y0, gamma, beta, bn.running_mean, bn.running_var,
-                                              bn.num_batches_tracked if training else None, bn.eps, bn.momentum, 1, training)
+            out, *st = bn_relu_up(y0, gamma, beta, bn)
         if keep is not None:
             keep.update(x=x, w=w, y0=y0, bn=tuple(st), pooled=pooled, out=out)
         ctx.stride, ctx.pooled, ctx.training, ctx.keep = stride, pooled, training, keep
@@ -188,12 +183,7 @@ def native_reason(layer0, x):
                         aligned=True, takes_grad=False)
     if why is not None:
         return why
-    for t in list(layer0.parameters()) + list(layer0.buffers()):
-        if t.device != x.device or (t.is_floating_point() and t.dtype != torch.float32):
-            return "layer0: a parameter or buffer is not a float32 tensor on x's device"
-    if not any(p.requires_grad for p in layer0.parameters()):
-        return "nothing to differentiate"
-    return None
+    return _placement_reason(x, layer0.parameters(), layer0.buffers(), "layer0: ")      # (x takes no grad: refused above)
 
 
 def forward_fp32_stem(layer0, x, keep=None):
@@ -204,6 +194,5 @@ def forward_fp32_stem(layer0, x, keep=None):
     Nb, _, H, W = x.shape
     Ho, Wo = _out_hw(H, W, stride)
     if bn.training and Nb * Ho * Wo == 1:      # the framework's error for one value per channel, before any launch
-        raise ValueError("Expected more than 1 value per channel when training, got input size %s"
-                         % ((Nb, conv.out_channels, Ho, Wo),))
+        raise _one_value_error((Nb, conv.out_channels, Ho, Wo))
     return CodenetStemFp32Function.apply(x, (stride, bn, pool is not None), keep, conv.weight, bn.weight, bn.bias)

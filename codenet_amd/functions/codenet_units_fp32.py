@@ -38,9 +38,9 @@ from torch.autograd.function import once_differentiable
 from .. import _native as N_
 from .. import ops
 from . import codenet_stage as CS
-from ._qat_common import _hook_reason, _input_reason, _is_1x1, _is_dw
+from ._fp32_common import (_bn_reason, _hook_reason, _input_reason, _is_1x1, _is_dw, _one_value_error, _out_hw,
+                           _placement_reason, bn_backward2, bn_stats)
 from .codenet_bn import BnReluUpsample
-from .codenet_heads_fp32 import _bn_reason, bn_backward2, bn_stats
 from .codenet_units import PointwiseRangeFunction, _pointwise, _transposed
 
 # A/B switch (tools/units_fp32_bench.py): the fp32 units and layer4 of a training step on the kernels above (True) or module
@@ -52,10 +52,6 @@ _p = CS._p
 
 def _ws(Nb, C, H, W, device):
     return CS._workspace(N_.lib().cdn_codenet_unit_fp32_workspace_bytes(Nb, C, H, W), device)
-
-
-def _out_hw(H, W, stride):
-    return (H - 1) // stride + 1, (W - 1) // stride + 1
 
 
 def _dw_forward(in_ptr, in_pitch, st, gamma, beta, w, Nb, C, H, W, stride, like):
@@ -354,16 +350,7 @@ def native_reason(node_or_layer, x):
     why = _input_reason(x, widest, channels=cin, aligned=True)
     if why is not None:
         return why
-    for t in list(node_or_layer.parameters()) + list(node_or_layer.buffers()):
-        if t.device != x.device or (t.is_floating_point() and t.dtype != torch.float32):
-            return "a parameter or buffer is not a float32 tensor on x's device"
-    if not (x.requires_grad or any(p.requires_grad for p in node_or_layer.parameters())):
-        return "nothing to differentiate"
-    return None
-
-
-def _one_value_error(shape):
-    return ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(shape),))
+    return _placement_reason(x, node_or_layer.parameters(), node_or_layer.buffers())
 
 
 def forward_fp32_units(layer, x, keep=None):

@@ -98,13 +98,13 @@ BUDGET_BN_TRAIN = {"bn_stats_kernel": 64, "bn_apply_kernel": 64, "bn_bwd1_kernel
 # no scratch
 BUDGET_HEADS_FP32_TRAIN = {"head32_dw_fwd_kernel": 64, "head32_tail_fwd_kernel": 64, "head32_dw_bwd_kernelILb": 128,
                            "head32_tail_bwd_kernelILi": 64, "head32_bn_bwd2_kernel": 64, "head32_tail_bwd_finish_kernel": 64,
-                           "head32_dw_bwd_finish_kernel": 64, "bn_stats_kernel": 64, "bn_bwd1_kernelILi1": 64,
+                           "dw_bwd_finish_kernel": 64, "bn_stats_kernel": 64, "bn_bwd1_kernelILi1": 64,
                            "bn_stats_finish_kernel": 64, "bn_bwd_finish_kernel": 64, "bn_eval_stats_kernel": 64}
 # codenet_units_fp32_train.hip (the fp32 units in training), from the compiled code: the depthwise
 # forward 37-62 VGPRs (the scalar stride-2 loader is the widest), the apply / join kernels 21-30, the first backward pass
 # 22-36, the depthwise backward 62-93 (stride 1 on the raw input is the widest); no scratch, no spills
 BUDGET_UNITS_FP32_TRAIN = {"unit32_dw_fwd_kernel": 64, "unit32_apply_kernel": 32, "unit32_bwd1_kernel": 40,
-                           "unit32_dw_bwd_kernelILi": 96, "unit32_dw_bwd_finish_kernel": 32}
+                           "unit32_dw_bwd_kernelILi": 96, "dw_bwd_finish_kernel": 32}
 # codenet_stem_fp32_train.hip (the fp32 stem in training), from the compiled code: the pool forward
 # with its 3 x 9 window 41-54 VGPRs, the first backward pass without the pool (cdn_bn.h's bn_bwd1_kernel without its store)
 # 22-28, with the pool 52 (the per-pixel gather) and 81 (the 5 x 7 patch of the 16-byte path); the weight gradient holds

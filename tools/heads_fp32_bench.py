@@ -37,6 +37,7 @@ import qat_bench
 from fp32_block_bench import _median_ms
 from codenet_amd import harness, ops, pipeline
 from codenet_amd.functions import codenet_heads as CH
+from codenet_amd.functions import _fp32_common as F32
 from codenet_amd.functions import codenet_heads_fp32 as HF
 
 WIDTHS = {"hm": 20, "wh": 2, "reg": 2}
@@ -58,21 +59,21 @@ def kernel_rates(Nb=32, C=64, H=128, W=128):
     w3, b3 = (torch.randn(2, C, 1, 1, generator=g) / 8).cuda(), torch.zeros(2, device="cuda")
     bn = torch.nn.BatchNorm2d(C).cuda().train()
     S = y1.numel() * 4
-    st1 = HF.bn_stats(y1, bn)
+    st1 = F32.bn_stats(y1, bn)
     y2 = HF.dw_forward(y1, st1, gamma, beta, w2)
-    st2 = HF.bn_stats(y2, bn)
+    st2 = F32.bn_stats(y2, bn)
     gz2, _, _, means2, _, _ = HF.tail_backward(gy3, y2, st2, gamma, beta, w3)
     gz1, _, _, _, means1 = HF.dw_backward(gz2, y2, st2, gamma, means2, True, y1, st1, gamma, beta, w2)
     gy1 = torch.empty_like(y1)
     rm, rv = torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
     calls = {
         "bn_apply_kernel": (2, lambda: ops.bn_relu_up_forward(y1, gamma, beta, rm, rv, None, 1e-5, 0.1, 1, False)),
-        "bn_stats_kernel": (1, lambda: HF.bn_stats(y1, bn)),
+        "bn_stats_kernel": (1, lambda: F32.bn_stats(y1, bn)),
         "head32_dw_fwd_kernel": (2, lambda: HF.dw_forward(y1, st1, gamma, beta, w2)),
         "head32_tail_fwd_kernel": (1, lambda: HF.tail_forward(y2, st2, gamma, beta, w3, b3)),
         "head32_tail_bwd_kernel": (2, lambda: HF.tail_backward(gy3, y2, st2, gamma, beta, w3)),
         "head32_dw_bwd_kernel": (4, lambda: HF.dw_backward(gz2, y2, st2, gamma, means2, True, y1, st1, gamma, beta, w2)),
-        "head32_bn_bwd2_kernel": (3, lambda: HF.bn_backward2(gz1, y1, st1, gamma, means1, True, gy1, 0, C * H * W)),
+        "head32_bn_bwd2_kernel": (3, lambda: F32.bn_backward2(gz1, y1, st1, gamma, means1, True, gy1, 0, C * H * W)),
     }
     out = {}
     for name, (tensors, fn) in calls.items():

@@ -40,7 +40,7 @@ import torch
 import qat_bench
 from fp32_block_bench import _median_ms
 from codenet_amd import harness, ops, pipeline
-from codenet_amd.functions import codenet_heads_fp32 as HF
+from codenet_amd.functions import _fp32_common as F32
 from codenet_amd.functions import codenet_units as CU
 from codenet_amd.functions import codenet_units_fp32 as U32
 
@@ -97,9 +97,9 @@ def kernel_rates(Nb=32, C=58, H=128, W=128):
     w = (torch.randn(C, 1, 3, 3, generator=g) / 3).cuda()
     bn = torch.nn.BatchNorm2d(C).cuda().train()
     S, pitch = y1.numel() * 4, C * H * W
-    st1 = HF.bn_stats(y1, bn)
+    st1 = F32.bn_stats(y1, bn)
     y2 = {s: U32._dw_forward(y1.data_ptr(), pitch, st1, gamma, beta, w, Nb, C, H, W, s, y1) for s in (1, 2)}
-    st2 = {s: HF.bn_stats(y2[s], bn) for s in (1, 2)}
+    st2 = {s: F32.bn_stats(y2[s], bn) for s in (1, 2)}
     gz2 = {s: torch.randn_like(y2[s]) for s in (1, 2)}
     means2 = {s: U32._bn_backward_sums(gz2[s], y2[s], st2[s])[2] for s in (1, 2)}
     out, gx, gz1 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(y1)
