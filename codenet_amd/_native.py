@@ -62,6 +62,7 @@ _SIGNATURES = {
                                               + [_i, _vp, ctypes.c_size_t, _vp, _vp, _i, _vp, _vp, _vp]),
     "cdn_codenet_stage_fused_intermediates": (_i, [_i64] * 4 + [_i, _i, _i, _vp, _vp]),
     "cdn_codenet_wcodes_kb_columns": (_i64, [_i64, _i64]),
+    "cdn_codenet_pwi8s_resident_workgroups": (_i, [_i64]),
     "cdn_codenet_pointwise_i8_supported": (_i, [_i64] * 4),
     "cdn_quantact_arrive_words": (_i, []),
     "cdn_codenet_scale_forward_update": (_i, [_vp] * 4 + [_i64] * 4 + [_f, _f] + [_vp] * 4 + [_i, _d, _vp, _vp]),

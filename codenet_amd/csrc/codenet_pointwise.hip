@@ -883,19 +883,24 @@ pwi8h_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq, const
 // tiles is the serial sum of a global round trip, the fp32 -> code conversion, LDS writes, a barrier, LDS reads and the
 // MFMAs, with two workgroups per CU to overlap (DESIGN_HISTORY section 4.1).  Here a workgroup owns a 32-row block x
 // 32 TN columns, its four WAVES are the four quarters of K and each runs its own pipeline without workgroup barriers:
-//   A   32 rows x 32 k of fp32 d per window by LDS-DMA into a wave-private ring RR - 1 windows ahead (whole 128-byte
-//       lines, XOR-swizzled source chunks: pws_kernel); the fragment -- lane (i, h): k in [16 h, 16 h + 16) of row i --
-//       is read as four ds_read_b128 and converted IN REGISTERS to the two nibble operands (pwi8_kernel's ucode / perm
-//       expressions: every element is converted once per workgroup);
+//   A   32 rows x 32 k of fp32 d per window by LDS-DMA into a wave-private ring of RR = 2 windows, one window ahead
+//       (whole 128-byte lines, XOR-swizzled source chunks: pws_kernel); the fragment -- lane (i, h): k in
+//       [16 h, 16 h + 16) of row i -- is read as four ds_read_b128 and converted IN REGISTERS to the two nibble operands
+//       (pwi8_kernel's ucode / perm expressions: every element is converted once per workgroup);
 //   B   the weight codes from a K-BLOCKED copy [window][column][32 B] (behind the row-major codes, made by the host:
 //       CDN_X_WCODES_KB): the operand of a 32-column tile is one fully coalesced 1-KB load per window, straight into
 //       registers, one window ahead; 16 * qw by a byte shift.
 // The int32 partial sums of the four k quarters are added through LDS (exact: order-independent).  Same integer sums
 // and the same epilogue expression as pwi8_kernel: bit-identical outputs and ranges (tests/test_gpu_parity.py).
 // ncg = 2 (Co = 256): two workgroups per row block, 128 columns each, 8 ids apart -- the same XCD, dispatched
-// together, so the second reading of the A rows is an L2 hit; 1024 three-per-CU workgroups instead of 512 two-per-CU
-// ones, which is what lets prologues (4 us: cold instruction fetch + the first DMA round trip) and epilogues (7 us)
-// of some workgroups overlap the k loops of others -- with one round of workgroups the launch was the plain sum.
+// together, so the second reading of the A rows is an L2 hit.
+// Round 7: 36 KB of LDS (the epilogue's partial sums, which alias the four 8-KB rings) and 128 registers -- four
+// workgroups per CU, so the 1024 workgroups of CoDeNet1x's stage 0 are all resident (cdn_codenet_pwi8s_resident_workgroups;
+// before: rings of three windows, 48 KB, 160 registers, three per CU = 768 + a second round of 256).  Measured, three
+// interleaved rounds on one box: the launch 31.5 -> 31.1 us, the step 0.2532 -> 0.2506 ms; a ring of five HALF windows
+// (40 KB, three halves in flight) 31.5 us.  In-kernel stamps of that form: every workgroup starts within 0.6 us, but its
+// k loop takes 21.2 us instead of 11.5 -- sixteen waves per CU stream the 67 MB hardly faster than twelve did, and in
+// lockstep no epilogue overlaps a k loop (DESIGN.md sections 4.8 and 8).
 // Wide codes (state[6]): pwi8_wide_path.
 // vmcnt discipline: the weight loads are inline asm as well.  A compiler-visible load in this loop is waited for
 // with a count the compiler derives WITHOUT the DMAs it cannot see, and in-order completion then makes every such
@@ -904,6 +909,9 @@ pwi8h_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq, const
 // peeled) -- a conditional load makes the register a phi, and the copy the compiler then inserts reads it before the
 // wait (second version: wrong sums); tools/check_asm_loads.py scans the ISA for exactly that.
 // ------------------------------------------------------------------------------------------
+// dynamic LDS of a workgroup: the epilogue's partial sums [4 waves][64 columns][32 + 4 rows] of int32 (36 KB), which alias
+// the four rings of two 4-KB windows (32 KB) and the wide path's tiles
+constexpr int kPwi8sLds = 4 * 64 * 36 * 4;
 // the int8 part of pwi8s_kernel (a function of its own so that the kernel is a plain if / else of the two paths: with
 // the wide branch written as an early return in front of it the compiler saw that branch's pending stores on a path
 // into the prologue below and put an s_waitcnt vmcnt(0) between the first weight loads -- i.e. behind the first DMAs)
@@ -914,7 +922,7 @@ __device__ __forceinline__ void pwi8s_body(const float *__restrict__ A, const si
                                            const cdn::QUpdate &qu, long M, int K, int Co, int relu, int lda, int ldo,
                                            const int *__restrict__ omap, int ncg, long m0, int cb, float qs, float qz,
                                            char *lds) {
-  constexpr int kRing = RR * 4096;
+  constexpr int kRing = RR * 4096;                   // windows of 32 rows x 32 k of fp32
   // Nothing is in flight here, and the compiler is told so with a REAL s_waitcnt vmcnt(0) (the builtin, which its
   // wait-count bookkeeping sees): the structurised control flow has an edge from the end of the wide branch to this
   // block, and for the stores pending on that edge it otherwise puts its own vmcnt(0) in front of the first asm load
@@ -924,7 +932,9 @@ __device__ __forceinline__ void pwi8s_body(const float *__restrict__ A, const si
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 31, h = lane >> 5;
   const int Cot = 32 * TN * ncg;                     // columns per window of the k-blocked codes (zero rows behind Co)
-  const int ioff = (int)qz + (2048 - 128) - 0x4B400000;
+  // (wave-uniform values of the conversion in scalar registers, said so: as vector registers they were two of the 128)
+  const int ioff = __builtin_amdgcn_readfirstlane((int)qz + (2048 - 128) - 0x4B400000);
+  const int umax = __builtin_amdgcn_readfirstlane(4087);
   // k windows (32 channels) of this wave: whole PAIRS of windows, the first (K / 64) % 4 waves one pair more -- every
   // wave runs an even number of steps (the two weight-register sets alternate without a copy)
   const int pairs = K >> 6;
@@ -941,13 +951,18 @@ __device__ __forceinline__ void pwi8s_body(const float *__restrict__ A, const si
       const int row = 8 * u + dr;
       const int rl = (int)(row < rmax ? row : rmax);
       aoff[u] = (unsigned)rl * (unsigned)lda * 4u + (unsigned)((dc ^ ((row >> 1) & 7)) * 16);
+      // one register per offset for the whole kernel: left alone, the compiler keeps a second, differently derived copy
+      // for the peeled steps (128 registers are four workgroups per CU, and that copy was the difference)
+      asm volatile("" : "+v"(aoff[u]));
     }
   }
   const unsigned ring = cdn::lds_addr_uniform(lds) + (unsigned)w * kRing;
   auto issue = [&](int t) {
     const unsigned dst = ring + (unsigned)(t % RR) * 4096;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) cdn::glds16(abase, aoff[u] + (unsigned)t * 128u, dst + u * 1024);
+    // (the window's k offset goes into the wave-uniform base: added to the lanes' offsets it made the compiler keep a
+    // second, advancing copy of them for the loop, and the originals were spilled across it)
+    for (int u = 0; u < 4; ++u) cdn::glds16(abase + t * 32, aoff[u], dst + u * 1024);
   };
   // ---- B: one coalesced 16-byte load per lane, tile and window (inline asm: see the header) -----------------------------
   const unsigned long long wb = (unsigned long long)(Wkb + ((long)win0 * Cot + cb) * 32);
@@ -973,34 +988,41 @@ __device__ __forceinline__ void pwi8s_body(const float *__restrict__ A, const si
     const float y_p = qs * v;      // (two roundings, as the reference: see pwi8_kernel)
     const float y = (y_p - qz) + 12582912.0f;
     int u = (int)__float_as_uint(y) + ioff;
-    u = min(max(u, 8), 4087);
+    u = min(max(u, 8), umax);
     return (unsigned)u;
   };
   i32x16 acc[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) acc[j] = (i32x16){0};
   const char *wring = lds + w * kRing;
-  const int frow = i * 128, fsw = (i >> 1) & 7;
-  // issue order (vmcnt counts DMAs and loads alike, completing in order):
-  //   A(0) .. A(RR-3), B(0), A(RR-2) | step t: B(t+1), A(t+RR-1), wait, compute(t)
-  // so that behind B(t) -- and A(t), older still -- there are A(t+RR-2), B(t+1), A(t+RR-1): TN + 8 in the loop
-  CDN_STAMPR(2, 1);      // (in front of the first DMA: a store here would be one more count behind every wait)
+  // the fragment's four chunks within a window (as aoff: one register each for the loop and the peeled step alike)
+  unsigned foff[4];
 #pragma unroll
-  for (int t = 0; t < RR - 2; ++t) issue(t);
+  for (int q = 0; q < 4; ++q) {
+    foff[q] = (unsigned)(i * 128 + ((4 * h + q) ^ ((i >> 1) & 7)) * 16);
+    asm volatile("" : "+v"(foff[q]));
+  }
+  // issue order (vmcnt counts DMAs and loads alike, completing in order):
+  //   B(0), A(0) | step t: B(t+1), A(t+1), wait, compute(t)
+  // Step t reads the slot of window t while window t + 1 lands in the other one, which step t - 1 read: behind A(t) --
+  // and B(t), older still -- there are B(t+1) and A(t+1), TN + 4 in the loop.
+  static_assert(RR == 2, "prologue, look-ahead and the peeled step are written for a ring of two windows");
+  CDN_STAMPR(2, 1);      // (in front of the first DMA: a store here would be one more count behind every wait)
   loadB(bA, 0);
-  issue(RR - 2);
-  auto step = [&](int t, i32x4 (&bcur)[TN], i32x4 (&bnxt)[TN], auto more_b, auto more_a, auto prev_a) {
-    // behind B(t) there are: A(t+RR-2) if the step before (or the prologue) issued it, B(t+1), A(t+RR-1)
-    constexpr int MB = decltype(more_b)::value, MA = decltype(more_a)::value, PA = decltype(prev_a)::value;
-    if constexpr (MB) loadB(bnxt, t + 1);
-    if constexpr (MA) issue(t + RR - 1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(TN * MB + 4 * MA + 4 * PA) : "memory");
+  issue(0);
+  auto step = [&](int t, i32x4 (&bcur)[TN], i32x4 (&bnxt)[TN], auto more) {
+    constexpr int MORE = decltype(more)::value;      // a window behind this one: its weights and its DMAs go out first
+    if constexpr (MORE) {
+      loadB(bnxt, t + 1);
+      issue(t + 1);
+    }
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((TN + 4) * MORE) : "memory");
     release(bcur);
     const char *slot = wring + (t % RR) * 4096;
     i32x4 a0, a1;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float4 v = *reinterpret_cast<const float4 *>(slot + frow + ((4 * h + q) ^ fsw) * 16);
+      const float4 v = *reinterpret_cast<const float4 *>(slot + foff[q]);
       const unsigned u0 = ucode(v.x), u1 = ucode(v.y), u2 = ucode(v.z), u3 = ucode(v.w);
       const unsigned p01 = u0 | (u1 << 16), p23 = u2 | (u3 << 16);
       a0[q] = (int)(__builtin_amdgcn_perm(p23, p01, 0x06040200u) & 0x0F0F0F0Fu);
@@ -1016,19 +1038,18 @@ __device__ __forceinline__ void pwi8s_body(const float *__restrict__ A, const si
       acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, s16, acc[j], 0, 0, 0);
     }
   };
-  // nit is even and >= RR: every step of the loop fetches the A window RR - 1 ahead and the weights one ahead; the last
-  // steps are peeled with their own (static) counts -- no branch and no register copy anywhere near a wait
-  static_assert(RR == 3, "the peeled tail is written for a ring of three windows");
+  // nit is even and >= 2: every step but the last fetches the window and the weights one ahead; the last step is peeled
+  // with its own (static) count -- no branch and no register copy anywhere near a wait
   {
     const std::true_type y;
     const std::false_type n;
     int t = 0;
     for (; t + 2 < nit; t += 2) {
-      step(t, bA, bB, y, y, y);
-      step(t + 1, bB, bA, y, y, y);
+      step(t, bA, bB, y);
+      step(t + 1, bB, bA, y);
     }
-    step(t, bA, bB, y, n, y);
-    step(t + 1, bB, bA, n, n, n);
+    step(t, bA, bB, y);
+    step(t + 1, bB, bA, n);      // nothing behind
   }
   CDN_STAMPR(2, 2);
   // ---- epilogue: the four k quarters' int32 partial tiles through LDS (exact), two 32-column tiles per round ----------
@@ -1036,8 +1057,14 @@ __device__ __forceinline__ void pwi8s_body(const float *__restrict__ A, const si
   float mn = INFINITY, mx = -INFINITY;
   bool has_nan = false;      // a NaN among the tracked values: fminf / fmaxf drop it, the reference's min() / max() do not
   {
+    // the epilogue's indices from a thread id the compiler cannot look through: derived from the one above, their
+    // addresses are computed in front of the k loop and held in registers across it
+    int etid = tid;
+    asm volatile("" : "+v"(etid));
+    const int tid = etid, i = tid & 31, h = (tid >> 5) & 1, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     int *P = reinterpret_cast<int *>(lds);
     constexpr int PLD = 36;                           // ints per column: 32 rows + 4 (16-byte aligned, bank-staggered)
+    static_assert(4 * 64 * PLD * 4 == kPwi8sLds && 4 * kRing <= kPwi8sLds, "the partial sums alias the rings");
     const int col = tid & 63, r0 = (tid >> 6) * 8;
     for (int j0 = 0; j0 < TN; j0 += 2) {
       __syncthreads();                                // (rings drained / the previous round's sums read)
@@ -1089,7 +1116,7 @@ __device__ __forceinline__ void pwi8s_body(const float *__restrict__ A, const si
 }
 
 template <int TN, int RR>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
 pwi8s_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq, const signed char *__restrict__ Wkb,
              const float *__restrict__ wscale, const int *__restrict__ wsum, const float *__restrict__ Wp,
              const float *__restrict__ bias, float *__restrict__ R, cdn::QUpdate qu, long M, int K,
@@ -1709,6 +1736,17 @@ static bool pwi8s_applies(long M, int64_t Kt, int Cpad, int64_t Co, bool pw_fast
   return w_kb != nullptr && pw_fast && Kt == Cpad && wcodes_kb_columns(Kt, Co) != 0 && M >= 1 &&
          2 * cdn::ceil_div(M, 32) <= (long)kMaxGrid;
 }
+// the streaming kernel's instantiation for Co columns (its dynamic LDS: kPwi8sLds)
+using Pwi8sKernel = decltype(&pwi8s_kernel<4, 2>);
+static Pwi8sKernel pwi8s_choice(int64_t Co) { return Co <= 64 ? pwi8s_kernel<2, 2> : pwi8s_kernel<4, 2>; }
+// diagnostics: workgroups of that instantiation the runtime keeps resident per CU at the launch's LDS size (0: no
+// streaming kernel for this Co, negative: the runtime's error)
+extern "C" int cdn_codenet_pwi8s_resident_workgroups(int64_t Co) {
+  if (Co < 1 || Co > 256) return 0;
+  int n = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)pwi8s_choice(Co), 256, kPwi8sLds);
+  return e == hipSuccess ? n : -(int)e;
+}
 extern "C" int64_t cdn_codenet_wcodes_kb_columns(int64_t C, int64_t Co) {
   return C > 0 ? wcodes_kb_columns((C + 63) / 64 * 64, Co) : 0;
 }
@@ -1773,8 +1811,8 @@ int cdn::launch_pointwise(const cdn::PwCall &p) {
       const long nrb = cdn::ceil_div(M, 32);
       const int ncg = Co > 128 ? 2 : 1;
       const unsigned grid = (unsigned)(nrb * ncg);
-      constexpr int kLds = 4 * 3 * 4096;
-      auto kern = Co <= 64 ? pwi8s_kernel<2, 3> : pwi8s_kernel<4, 3>;
+      auto kern = pwi8s_choice(Co);
+      constexpr int kLds = kPwi8sLds;
       kern<<<grid, 256, kLds, st>>>(p.a, p.a_state, p.w_kb, p.w_scale, p.w_colsum, p.w, p.bias, p.out, p.qu, M, (int)Kt,
                                     (int)Co, p.relu, (int)lda, (int)ldo, p.out_map, (int)C, ncg);
       return cdn::check_launch("codenet int8 pointwise (streaming)");

@@ -525,6 +525,10 @@ int cdn_codenet_stage_fused_supported(int64_t N, int64_t C, int64_t H, int64_t W
 #define CDN_X_WCODES_KB 0x800
 int64_t cdn_codenet_wcodes_kb_columns(int64_t C, int64_t Co);
 int64_t cdn_codenet_wcodes_kb_offset(int64_t C, int64_t Co);
+/* Diagnostics: the workgroups of the streaming int8 pointwise kernel (the instantiation taken for Co output columns, at
+ * the launch's LDS size) that the runtime keeps resident per CU.  0: no such kernel for this Co; negative: the runtime's
+ * error code. */
+int cdn_codenet_pwi8s_resident_workgroups(int64_t Co);
 /* | CDN_X_DEFER_RANGE and the phase bits (round 5; SURVEY.md section 8e, collective 3 -- the multi-process parity mode in
  * which R ranks x B images track the ranges of ONE R*B-image run; the reference's only multi-GPU mechanism,
  * lib/models/data_parallel.py:64-84, scatters one batch and so has batch-global ranges by construction): the stage call

@@ -27,3 +27,13 @@ for r in rows[a:b]:
 for (n, wgs, threads), (cnt, dur, lds) in seen.items():
     print("%-44s x%2d  workgroups %6d = %6.2f per CU  x %4d threads  static LDS %6d  avg %6.1f us"
           % (n, cnt, wgs, wgs / 256.0, threads, lds, dur / cnt))
+# pwi8s_kernel takes its LDS dynamically (the trace's static figure is 0 for it): how many of its workgroups a CU holds is
+# asked of the runtime, for the instantiation and LDS size of the launch (rounds of a launch = its per-CU figure / this)
+import os
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from codenet_amd import _native
+
+for co in (64, 128, 256):
+    print("%-44s Co %3d  resident workgroups per CU %d"
+          % ("pwi8s_kernel", co, _native.lib().cdn_codenet_pwi8s_resident_workgroups(co)))
