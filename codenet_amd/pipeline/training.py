@@ -3,7 +3,8 @@ layers 1-4 in front of that tail, or of the whole network from the image -- as o
 
 Part of codenet_amd.pipeline (split by concern in round 6; `from codenet_amd import pipeline` exposes every name as
 before)."""
-import os
+import collections
+import importlib
 
 import torch
 import torch.nn as nn
@@ -81,82 +82,121 @@ def _stage_blocks_ok(seq):
     return True
 
 
-def _outside_scope(net):
-    """None, or the reason why `net`, a DetectionTail / DetectionTrunk / DetectionNet, is outside the validated scope: its
-    stages are not the blocks above, or a part it holds is refused by the gate of the functions/ module that runs it.  (The
-    gates see the caller's grad mode: under no_grad every one refuses, so the predicates built on this are False there.)"""
-    from ..functions import codenet_heads, codenet_stem, codenet_units
-    if not _stage_blocks_ok(net.deconv_layers):
-        return "deconv_layers: not a Sequential of [quantised deform stage, Sequential(ReLU, QuantAct), Upsample] blocks"
-    gated = [("heads", codenet_heads, net.head_modules())]
-    gated += [(name, codenet_units, getattr(net, name)) for name in net.PARTS if name in ("layer1", "layer2", "layer3", "layer4")]
-    gated += [(name, codenet_stem, getattr(net, name)) for name in net.PARTS if name == "layer0"]
-    for name, gate, part in gated:
-        why = gate.native_reason(part, None)
+_Scope = collections.namedtuple("_Scope", "name predicate chain precision words shown_by")
+
+# What GraphedTrainStep accepts without `unvalidated=True`, one row per scope: its name (`GraphedTrainStep.scope_of`), its
+# public predicate, the chain class whose parts are judged (`_chain_reason`) or None for a stage stack (`_is_stack`), the
+# precision that picks the gates and their order below, the words of the constructor's error, and the test file that shows
+# its replays bit-identical to the eager steps.
+SCOPES = (
+    # The quantised stages -- this row and the `deconv_layers` part of the three QAT chains -- are judged by their classes
+    # alone (`_stage_blocks_ok`).  That is weaker than `block_ok` inside functions/codenet_stage.forward_stage_blocks, which
+    # also asks native_act_ok, global_range, the Upsample's mode and factor and hooks: a stack whose post-stage QuantAct has
+    # percentile=True is accepted here although forward_stage_blocks then takes seq(x).  Merging the two changes answers: left as it is (DESIGN.md
+    # section 4.3, "The scope table").
+    _Scope("stage stack", "is_stage_stack", None, "qat",
+           "a stack of quantised deform stages (pipeline.build_hot_path, a quantised deconv_layers)",
+           "tests/test_train_step.py"),
+    _Scope("fp32 stack", "is_fp32_stage_stack", None, "fp32",
+           "the fp32 stack (a pipeline.DeconvLayers of [deform stage, BatchNorm2d, ReLU, Upsample] blocks)",
+           "tests/test_gpu_bn_block.py"),
+    _Scope("QAT tail", "is_native_tail", DetectionTail, "qat",
+           "a pipeline.DetectionTail of a quantised model whose heads run natively", "tests/test_gpu_heads_train.py"),
+    _Scope("QAT trunk", "is_native_trunk", DetectionTrunk, "qat",
+           "a pipeline.DetectionTrunk of a quantised model whose units also run natively", "tests/test_gpu_units_train.py"),
+    _Scope("QAT net", "is_native_net", DetectionNet, "qat",
+           "a pipeline.DetectionNet of a quantised model whose stem also runs natively", "tests/test_gpu_stem_train.py"),
+    _Scope("fp32 tail", "is_fp32_tail", DetectionTail, "fp32",
+           "the fp32 tail (a pipeline.DetectionTail of an fp32 model: those blocks and the fp32 heads)",
+           "tests/test_gpu_heads_fp32.py"),
+    _Scope("fp32 trunk", "is_fp32_trunk", DetectionTrunk, "fp32",
+           "the fp32 trunk (a pipeline.DetectionTrunk of an fp32 model: layers 1-4 in front of that tail)",
+           "tests/test_gpu_units_fp32.py"),
+    _Scope("fp32 net", "is_fp32_net", DetectionNet, "fp32",
+           "the fp32 network (a pipeline.DetectionNet of an fp32 model: the fp32 stem, judged with the example image, in "
+           "front of that trunk)", "tests/test_gpu_stem_fp32.py"),
+)
+_ROW = {s.predicate: s for s in SCOPES}
+
+# Per precision: the functions/ module whose native_reason(part, x) gates each part (None: `_stage_blocks_ok` alone), the
+# order in which the parts of a chain are asked -- it decides which reason is reported first -- and the text for a
+# `deconv_layers` that is no sequence of that precision's blocks at all.
+_LAYERS = ("layer1", "layer2", "layer3", "layer4")
+_GATES = {"qat": dict(dict.fromkeys(_LAYERS, "codenet_units"), layer0="codenet_stem", deconv_layers=None,
+                      heads="codenet_heads"),
+          "fp32": dict(dict.fromkeys(_LAYERS, "codenet_units_fp32"), layer0="codenet_stem_fp32", deconv_layers="codenet_bn",
+                       heads="codenet_heads_fp32")}
+_ORDER = {"qat": ("deconv_layers", "heads") + _LAYERS + ("layer0",),
+          "fp32": ("layer0",) + _LAYERS + ("deconv_layers", "heads")}
+_NOT_STAGES = {"qat": "not a Sequential of [quantised deform stage, Sequential(ReLU, QuantAct), Upsample] blocks",
+               "fp32": "not a Sequential of [deform stage, BatchNorm2d, ReLU, Upsample] blocks"}
+
+
+def _part_reason(precision, name, part, x=None):
+    """None, or the reason -- the gate's own words -- why `part`, the part `name` of a net, is outside the scopes of
+    `precision`.  x None: the modules alone are judged.  The QAT gates see the caller's grad mode (under no_grad every one
+    refuses); the fp32 gates are asked with grad mode on: their answer is a property of the modules.  The gate is looked up
+    at every call, so a NATIVE_* switch of its module counts from the moment it is flipped."""
+    if name == "deconv_layers" and not (_stage_blocks_ok(part) if precision == "qat"
+                                        else isinstance(part, nn.Sequential) and len(part) > 0):
+        return _NOT_STAGES[precision]
+    gate = _GATES[precision][name]
+    if gate is None:
+        return None
+    with torch.set_grad_enabled(precision == "fp32" or torch.is_grad_enabled()):
+        return importlib.import_module("..functions." + gate, __package__).native_reason(part, x)
+
+
+def _chain_reason(net, precision, example_inputs=None):
+    """None, or "<part>: <reason>" for the first part of `net`, a DetectionTail / DetectionTrunk / DetectionNet, that
+    `_part_reason` refuses, asked in `_ORDER[precision]`.  example_inputs None: the modules alone are judged; else the fp32
+    stem is also judged on the image the capture will see (example_inputs[0]) -- one that requires grad, lives on the CPU or
+    is not float32 contiguous would silently put the stem back on the framework's backward."""
+    for name in _ORDER[precision]:
+        if name != "heads" and name not in net.PARTS:
+            continue
+        part = net.head_modules() if name == "heads" else getattr(net, name)
+        why = _part_reason(precision, name, part)
+        if (precision, name) == ("fp32", "layer0"):
+            if why is None and example_inputs is not None:
+                why = _part_reason(precision, name, part, example_inputs[0]) if example_inputs else "no example image to judge"
+            if why is not None and isinstance(part, nn.Sequential) and len(part) and type(part[0]) is nn.Conv2d:
+                why = "the fp32 stem: " + why      # (a quantised stem keeps the gate's words alone)
         if why is not None:
             return "%s: %s" % (name, why)
     return None
 
 
-def _fp32_tail_outside_scope(net):
-    """None, or the reason why `net`, a DetectionTail, is not the fp32 tail GraphedTrainStep.is_fp32_tail accepts."""
-    from ..functions import codenet_bn, codenet_heads_fp32
-    seq = net.deconv_layers
-    if not isinstance(seq, nn.Sequential) or len(seq) == 0:
-        return "deconv_layers: not a Sequential of [deform stage, BatchNorm2d, ReLU, Upsample] blocks"
-    with torch.enable_grad():      # (a property of the modules, as is_fp32_stage_stack)
-        why = codenet_bn.native_reason(seq, None)
-        if why is not None:
-            return "deconv_layers: %s" % why
-        why = codenet_heads_fp32.native_reason(net.head_modules(), None)
-    return "heads: %s" % why if why is not None else None
+def _is_stack(net, precision):
+    """True for a stage stack of `precision`: a sequence that `_part_reason` accepts as `deconv_layers`, in a container whose
+    forward runs it through functions/codenet_stage.forward_stage_blocks.  QAT: the Sequential itself, or a module whose
+    only child it is.  fp32: a pipeline.DeconvLayers with its own forward whose only child it is -- a bare Sequential, or
+    another container, runs ``Sequential.forward``: the framework's BatchNorm under autograd."""
+    from .common import DeconvLayers
+    seq = getattr(net, "deconv_layers", net)
+    if _part_reason(precision, "deconv_layers", seq) is not None:
+        return False
+    only_child = [m for m in net.children()] == [seq]
+    if precision == "qat":
+        return seq is net or only_child
+    return isinstance(net, DeconvLayers) and type(net).forward is DeconvLayers.forward and only_child
 
 
-def _fp32_trunk_outside_scope(net):
-    """None, or the reason why `net`, a DetectionTrunk, is not the fp32 trunk GraphedTrainStep.is_fp32_trunk accepts: layers
-    1-4 that functions/codenet_units_fp32 refuses, or a tail that `_fp32_tail_outside_scope` refuses."""
-    from ..functions import codenet_units_fp32
-    with torch.enable_grad():      # (a property of the modules, as is_fp32_tail)
-        for name in ("layer1", "layer2", "layer3", "layer4"):
-            why = codenet_units_fp32.native_reason(getattr(net, name), None)
-            if why is not None:
-                return "%s: %s" % (name, why)
-    return _fp32_tail_outside_scope(net)
+def _accepts(scope, net, example_inputs=None):
+    """Whether `net` is in `scope`, a row of SCOPES."""
+    if scope.chain is None:
+        return _is_stack(net, scope.precision)
+    return isinstance(net, scope.chain) and _chain_reason(net, scope.precision, example_inputs) is None
 
 
-def _fp32_stem_reason(net, example_inputs):
-    """None, or the reason why the fp32 stem of `net`, a DetectionNet, would not run natively on the example image: the gate
-    of functions/codenet_stem_fp32 on the modules AND on the image the capture will see -- an image that requires grad,
-    lives on the CPU or is not float32 contiguous would silently put the stem back on the framework's backward."""
-    from ..functions import codenet_stem_fp32
-    with torch.enable_grad():
-        why = codenet_stem_fp32.native_reason(net.layer0, None)
-        if why is not None:
-            return why
-        if not example_inputs:
-            return "no example image to judge"
-        return codenet_stem_fp32.native_reason(net.layer0, example_inputs[0])
-
-
-def _fp32_net_outside_scope(net):
-    """None, or the reason why `net`, a DetectionNet, is not the fp32 network GraphedTrainStep.is_fp32_net accepts: a stem
-    that functions/codenet_stem_fp32 refuses, or a trunk that `_fp32_trunk_outside_scope` refuses."""
-    from ..functions import codenet_stem_fp32
-    with torch.enable_grad():      # (a property of the modules, as is_fp32_trunk)
-        why = codenet_stem_fp32.native_reason(net.layer0, None)
-    return "layer0: %s" % why if why is not None else _fp32_trunk_outside_scope(net)
-
-
-def _fp32_net_reason(net, example_inputs):
-    """The bracket of the constructor's error for `net`, a DetectionNet: for an fp32 stem (its first module is a Conv2d) what
-    the stem's gate says about the modules and the example image, behind "layer0: the fp32 stem: "; where the stem is
-    accepted, or is no fp32 stem at all, the reason of `_fp32_net_outside_scope` (the trunk's, or the stem's structure)."""
-    l0 = net.layer0
-    if isinstance(l0, nn.Sequential) and len(l0) and type(l0[0]) is nn.Conv2d:
-        why = _fp32_stem_reason(net, example_inputs)
-        if why is not None:
-            return "layer0: the fp32 stem: %s" % why
-    return _fp32_net_outside_scope(net)
+def _refusal(net, example_inputs):
+    """The constructor's error for a `net` outside every scope: the scopes, each chain scope of the class of `net` with the
+    reason why `net` is outside it."""
+    scopes = ["%s [%s]" % (s.words, _chain_reason(net, s.precision, example_inputs))
+              if s.chain is not None and isinstance(net, s.chain) else s.words for s in SCOPES]
+    return ("GraphedTrainStep is validated (bit-identical replays) only for: %s. `net` holds other modules, whose "
+            "PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass unvalidated=True to capture it "
+            "anyway (see the class docstring for what was measured)." % "; ".join(scopes))
 
 
 class GraphedTrainStep:
@@ -177,35 +217,21 @@ class GraphedTrainStep:
     exactly as in the eager loop.  `warmup` eager steps run first on a side stream (they DO train: allocator and lazily
     derived tensors settle before capture); the capture records on that same stream.
 
-    SCOPE.  Validated -- and accepted without `unvalidated=True` -- are (1) the stack of deform stages
-    (``pipeline.build_hot_path`` / a quantised ``deconv_layers``, `is_stage_stack`) and (2) the detection tail,
-    ``pipeline.DetectionTail(model)`` of a quantised model whose heads run on functions/codenet_heads.py
-    (`is_native_tail`), and (3) the trunk, ``pipeline.DetectionTrunk(model)`` -- layers 1-4 of the backbone in front of
-    that tail, from layer0's output -- of a quantised model whose units run on functions/codenet_units.py
-    (`is_native_trunk`), and (4) the whole network, ``pipeline.DetectionNet(model)`` -- the stem in front of that trunk,
-    from the image -- of a quantised model whose stem runs on functions/codenet_stem.py (`is_native_net`): every kernel of
-    those steps is this library's, every sum has one order; and (5) the fp32 stack of the reference's main.py --
-    ``pipeline.build_hot_path(quantized=False)``: a ``pipeline.DeconvLayers`` (its forward is forward_stage_blocks) of
-    [deform stage, BatchNorm2d, ReLU, Upsample] blocks, BatchNorm in training or eval mode (`is_fp32_stage_stack`; functions/codenet_bn.py, DESIGN.md section 4.3e;
-    tests/test_gpu_bn_block.py shows its replays bit-identical to the eager step); and (6) the fp32 tail,
-    ``pipeline.DetectionTail(model)`` of an fp32 model: those blocks in front of the fp32 detection heads [Conv2d 1x1,
-    BatchNorm2d, ReLU, depthwise Conv2d 3x3, BatchNorm2d, ReLU, Conv2d 1x1] on functions/codenet_heads_fp32.py, every
-    BatchNorm in training or eval mode (`is_fp32_tail`; tests/test_gpu_heads_fp32.py shows its
-    replays with the native criterion bit-identical to the eager steps); and (7) the fp32 trunk,
-    ``pipeline.DetectionTrunk(model)`` of an fp32 model: layers 1-3 of ``harness.BaseNode`` units and layer4 [Conv2d 1x1,
-    BatchNorm2d, ReLU] on functions/codenet_units_fp32.py in front of that tail, from layer0's output, every BatchNorm in
-    training or eval mode (`is_fp32_trunk`; tests/test_gpu_units_fp32.py shows its replays with the
-    native criterion bit-identical to the eager steps); and (8) the fp32 network, ``pipeline.DetectionNet(model)`` of an fp32
-    model: the stem [Conv2d 3 -> 24, BatchNorm2d, ReLU(, MaxPool2d(3, 2, 1))] on functions/codenet_stem_fp32.py in front of
-    that trunk, from the image, every BatchNorm in training or eval mode (`is_fp32_net`; DESIGN.md section 4.3h;
-    tests/test_gpu_stem_fp32.py shows its replays with the native criterion bit-identical to the eager steps) -- accepted
-    when the gate also accepts the example image (a float32, contiguous GPU image that does not require grad): main.py's
-    whole step, image -> loss -> optimizer, is then one chain of this library's kernels.
-    tests/test_train_step.py::test_graphed_train_step_* show replays of (1) bit-identical to the eager step and
-    bit-identical from a restored state whatever else the process does in between (a second model built before the capture
-    taking its first eager steps, another framework model training, the allocator's free memory filled with NaN);
-    tests/test_gpu_heads_train.py shows replays of (2) with the native criterion bit-identical to the eager steps,
-    tests/test_gpu_units_train.py those of (3), tests/test_gpu_stem_train.py those of (4).
+    SCOPE.  Validated -- and accepted without `unvalidated=True` -- are the rows of `SCOPES` in this module: in each, every
+    kernel of the step is this library's and every sum has one order, and the test file named shows the replays (of a chain:
+    with the native criterion) bit-identical to the eager steps.  `scope_of` names the row of a net; `step.scope` keeps it.
+      `is_stage_stack`: the quantised deform stages, ``pipeline.build_hot_path()`` / a quantised ``deconv_layers``; tests/test_train_step.py
+      `is_fp32_stage_stack`: the fp32 stack of main.py, ``pipeline.build_hot_path(quantized=False)`` (section 4.3e); tests/test_gpu_bn_block.py
+      `is_native_tail`: ``pipeline.DetectionTail(model)``, quantised: those stages and the heads (4.3b); tests/test_gpu_heads_train.py
+      `is_native_trunk`: ``pipeline.DetectionTrunk(model)``, quantised: layers 1-4 in front of that tail (4.3c); tests/test_gpu_units_train.py
+      `is_native_net`: ``pipeline.DetectionNet(model)``, quantised: the stem in front of that trunk (4.3d); tests/test_gpu_stem_train.py
+      `is_fp32_tail`: the fp32 tail, ``pipeline.DetectionTail(model)`` of an fp32 model (4.3f); tests/test_gpu_heads_fp32.py
+      `is_fp32_trunk`: the fp32 trunk, ``pipeline.DetectionTrunk(model)`` of an fp32 model (4.3g); tests/test_gpu_units_fp32.py
+      `is_fp32_net`: the fp32 network, ``pipeline.DetectionNet(model)`` of an fp32 model and an example image its stem accepts (4.3h); tests/test_gpu_stem_fp32.py
+    What each part must be is the `native_reason` of the functions/ module that runs it (`_GATES`); BatchNorms may be in
+    training or eval mode.  test_graphed_train_step_* also show replays of the first row bit-identical from a restored state
+    whatever else the process does in between (a second model built before the capture taking its first eager steps, another
+    framework model training, the allocator's free memory filled with NaN).
     A network that also runs PyTorch-ROCm operators under autograd (a bare harness.PoseShuffleNetV2, whose forward
     dispatches on inference schedules the capture was never validated for -- wrap it in DetectionNet --, an fp32 or
     percentile stem, heads or units, NATIVE_STEM / NATIVE_HEADS / NATIVE_UNITS off) needs `unvalidated=True`; what was measured for it (tools/experiments/gts_probe*.py):
@@ -222,27 +248,9 @@ class GraphedTrainStep:
         (``codenet_amd.losses.CtdetLoss``: its sums are fixed-order slabs of this library's own kernels)."""
 
     def __init__(self, net, optimizer, loss_fn, example_inputs, warmup=3, unvalidated=False):
-        if not unvalidated and not self.is_stage_stack(net) and not self.is_fp32_stage_stack(net) \
-                and not self.is_native_tail(net) and not self.is_native_trunk(net) and not self.is_native_net(net) \
-                and not self.is_fp32_tail(net) and not self.is_fp32_trunk(net) \
-                and not (self.is_fp32_net(net) and _fp32_stem_reason(net, example_inputs) is None):
-            raise NotImplementedError(
-                "GraphedTrainStep is validated (bit-identical replays) for a stack of quantised deform stages, for the "
-                "fp32 stack (a pipeline.DeconvLayers of [deform stage, BatchNorm2d, ReLU, Upsample] blocks on functions/codenet_bn), for a "
-                "pipeline.DetectionTail whose heads run natively, for a pipeline.DetectionTrunk whose units run "
-                "natively and for a pipeline.DetectionNet whose stem runs natively only; `net` "
-                "holds other modules, whose PyTorch-ROCm kernels under autograd are not run-to-run deterministic. Pass "
-                "unvalidated=True to capture it anyway (see the class docstring for what was measured)."
-                + (" [%s]" % _outside_scope(net) if isinstance(net, _DetectionChain) else "")
-                + " Also validated: the fp32 tail, a pipeline.DetectionTail of an fp32 model whose [deform stage, BatchNorm2d, "
-                "ReLU, Upsample] blocks run on functions/codenet_bn and whose heads run on functions/codenet_heads_fp32"
-                + (" [%s]" % _fp32_tail_outside_scope(net) if isinstance(net, DetectionTail) else "")
-                + ", and the fp32 trunk, a pipeline.DetectionTrunk of an fp32 model whose layers 1-4 also run on "
-                "functions/codenet_units_fp32"
-                + (" [%s]" % _fp32_trunk_outside_scope(net) if isinstance(net, DetectionTrunk) else "")
-                + ", and the fp32 network, a pipeline.DetectionNet of an fp32 model whose stem also runs on "
-                "functions/codenet_stem_fp32 for the example image"
-                + (" [%s]" % _fp32_net_reason(net, example_inputs) if isinstance(net, DetectionNet) else "") + ".")
+        self.scope = self.scope_of(net, example_inputs or ())      # (None: only `unvalidated=True` lets it through)
+        if self.scope is None and not unvalidated:
+            raise NotImplementedError(_refusal(net, example_inputs or ()))
         self.static = [t.detach().clone() for t in example_inputs]
         for t, src in zip(self.static, example_inputs):
             t.requires_grad_(src.requires_grad)
@@ -264,82 +272,52 @@ class GraphedTrainStep:
             optimizer.step()
 
     @staticmethod
+    def scope_of(net, example_inputs=None):
+        """The name of the row of `SCOPES` that accepts `net`, or None.  example_inputs None: the modules alone are judged;
+        else, as the constructor does, the fp32 stem also judges example_inputs[0], the image the capture will see."""
+        return next((s.name for s in SCOPES if _accepts(s, net, example_inputs)), None)
+
+    # The public predicates: one view each of a row of SCOPES, the modules alone.
+
+    @staticmethod
     def is_stage_stack(net):
-        """True for a (container of one) Sequential of [quantised deform stage, Sequential(ReLU, QuantAct), Upsample]
-        blocks -- what functions/codenet_stage.forward_stage_blocks runs natively and the bit-level tests cover."""
-        seq = getattr(net, "deconv_layers", net)
-        return _stage_blocks_ok(seq) and (seq is net or [m for m in net.children()] == [seq])
+        """SCOPES row "stage stack": classes and container only, whatever the grad mode."""
+        return _accepts(_ROW["is_stage_stack"], net)
 
     @staticmethod
     def is_fp32_stage_stack(net):
-        """True for a pipeline.DeconvLayers -- the container whose forward IS functions/codenet_stage.forward_stage_blocks --
-        of fp32 blocks [DeformConvWithOffsetScaleBoundPositive, BatchNorm2d, ReLU, Upsample(x2, nearest)] that
-        functions/codenet_bn runs natively (native_reason(seq, None) is None: affine BatchNorms that track running statistics
-        with a float momentum, no hooks, NATIVE_FP32_BLOCKS on), BatchNorm in training or eval mode: the stage stack of the
-        reference's main.py.  A bare ``nn.Sequential`` of such blocks, or another container around it, is refused: calling it
-        runs ``Sequential.forward``, the framework's BatchNorm under autograd, which this scope does not cover."""
-        from ..functions.codenet_bn import native_reason
-        from .common import DeconvLayers
-        if not isinstance(net, DeconvLayers) or type(net).forward is not DeconvLayers.forward:
-            return False
-        seq = net.deconv_layers
-        if not isinstance(seq, nn.Sequential) or len(seq) == 0 or [m for m in net.children()] != [seq]:
-            return False
-        with torch.enable_grad():
-            return native_reason(seq, None) is None
-
-    @staticmethod
-    def is_fp32_tail(net):
-        """True for a pipeline.DetectionTail of an fp32 model: ``deconv_layers`` a Sequential of the blocks
-        `is_fp32_stage_stack` describes (functions/codenet_bn.native_reason(seq, None) is None) and heads that
-        functions/codenet_heads_fp32 runs natively (native_reason(heads, None) is None: the seven-module Sequential of
-        shufflenetv2_dcn.py:246-258 with affine BatchNorms that track running statistics with a float momentum, one hidden
-        width, no hooks, NATIVE_FP32_HEADS on), every BatchNorm in training or eval mode.  A property of the modules: the
-        caller's grad mode does not change the answer.  `is_native_tail` stays False for it."""
-        return isinstance(net, DetectionTail) and _fp32_tail_outside_scope(net) is None
-
-    @staticmethod
-    def is_fp32_trunk(net):
-        """True for a pipeline.DetectionTrunk of an fp32 model: a tail that `is_fp32_tail` would accept (the same stages and
-        heads) behind layers 1-3 and layer4 that functions/codenet_units_fp32 runs natively (native_reason(layer, None) is
-        None: exactly ``harness.BaseNode`` units of nn.Conv2d / nn.BatchNorm2d in the reference's geometry and layer4 =
-        [Conv2d 1x1, BatchNorm2d, ReLU], no conv bias, affine BatchNorms that track running statistics with a float
-        momentum, no hooks, NATIVE_FP32_UNITS on), every BatchNorm in training or eval mode.  A property of the modules: the
-        caller's grad mode does not change the answer.  `is_native_trunk` stays False for it."""
-        return isinstance(net, DetectionTrunk) and _fp32_trunk_outside_scope(net) is None
-
-    @staticmethod
-    def is_fp32_net(net):
-        """True for a pipeline.DetectionNet of an fp32 model: a trunk that `is_fp32_trunk` would accept (the same layers 1-4,
-        stages and heads) behind a stem that functions/codenet_stem_fp32 runs natively (native_reason(layer0, None) is None:
-        exactly Sequential(Conv2d 3 -> 24 3x3 without bias, BatchNorm2d, ReLU[, MaxPool2d(3, 2, 1)]) at stride 2 with the pool
-        or 4 without, an affine BatchNorm that tracks running statistics with a float momentum, no hooks, NATIVE_FP32_STEM
-        on).  A property of the modules: the caller's grad mode does not change the answer.  The constructor also judges the
-        example image (`_fp32_stem_reason`).  `is_native_net` stays False for it."""
-        return isinstance(net, DetectionNet) and _fp32_net_outside_scope(net) is None
+        """SCOPES row "fp32 stack": a property of the modules, whatever the caller's grad mode."""
+        return _accepts(_ROW["is_fp32_stage_stack"], net)
 
     @staticmethod
     def is_native_tail(net):
-        """True for a pipeline.DetectionTail whose stages are the blocks `is_stage_stack` accepts and whose heads
-        functions/codenet_heads.forward_heads runs natively (native_reason(heads, None) is None: quantised heads with
-        the default QuantAct settings, no hooks, NATIVE_HEADS on) -- stages, heads and, with losses.CtdetLoss, the
-        criterion are then one chain of this library's kernels."""
-        return isinstance(net, DetectionTail) and _outside_scope(net) is None
+        """SCOPES row "QAT tail": False under no_grad, as its gates are."""
+        return _accepts(_ROW["is_native_tail"], net)
 
     @staticmethod
     def is_native_trunk(net):
-        """True for a pipeline.DetectionTrunk whose stages and heads are what `is_native_tail` accepts and whose layers 1-3
-        and layer4 functions/codenet_units runs natively (native_reason(layer, None) is None: QuantBaseNode units with the
-        default QuantAct settings, no hooks, NATIVE_UNITS on)."""
-        return isinstance(net, DetectionTrunk) and _outside_scope(net) is None
+        """SCOPES row "QAT trunk": False under no_grad, as its gates are."""
+        return _accepts(_ROW["is_native_trunk"], net)
 
     @staticmethod
     def is_native_net(net):
-        """True for a pipeline.DetectionNet whose layers 1-4, stages and heads are what `is_native_trunk` accepts and whose
-        stem functions/codenet_stem runs natively (native_reason(layer0, None) is None: the quantised 3 -> 24 stem with the
-        default QuantAct settings, no hooks, NATIVE_STEM on) -- image -> loss -> optimizer is then one chain of this
-        library's kernels."""
-        return isinstance(net, DetectionNet) and _outside_scope(net) is None
+        """SCOPES row "QAT net": False under no_grad, as its gates are."""
+        return _accepts(_ROW["is_native_net"], net)
+
+    @staticmethod
+    def is_fp32_tail(net):
+        """SCOPES row "fp32 tail": a property of the modules, whatever the caller's grad mode."""
+        return _accepts(_ROW["is_fp32_tail"], net)
+
+    @staticmethod
+    def is_fp32_trunk(net):
+        """SCOPES row "fp32 trunk": a property of the modules, whatever the caller's grad mode."""
+        return _accepts(_ROW["is_fp32_trunk"], net)
+
+    @staticmethod
+    def is_fp32_net(net):
+        """SCOPES row "fp32 net", the modules alone: the constructor and `scope_of` also judge the example image."""
+        return _accepts(_ROW["is_fp32_net"], net)
 
     def set_lr(self, value, group=None):
         """Write a new learning rate where the captured step reads it: the param group's lr must be a device TENSOR

@@ -287,7 +287,7 @@ def test_constructor_judges_the_example_image():
     ok = S32.native_reason
     S32.native_reason = lambda layer0, x: ok(layer0, None)      # (stands for a GPU image: this test has no GPU)
     try:
-        with pytest.raises(NotImplementedError, match=r"functions/codenet_stem_fp32 for the example image "
+        with pytest.raises(NotImplementedError, match=r"the fp32 network \([^\[\]]*\) "      # (the scope's own words)
                                                       r"\[layer2: the layer: a hook on sub-module .3.b2.0."):
             G(pipeline.DetectionNet(hooked), None, None, [torch.zeros(2, 3, 64, 64)])
     finally:
