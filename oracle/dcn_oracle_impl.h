@@ -49,7 +49,7 @@ static T FN(bilinear)(const T *plane, int H, int W, T h, T w)
 /* _kernel.cu:116-142 (get_gradient_weight) / :499-523 (dmcn_get_gradient_weight). */
 static T FN(grad_weight_corner)(T ah, T aw, int h, int w, int H, int W)
 {
-    if (ah <= -1 || ah >= H || aw <= -1 || aw >= W) return 0;
+    if (!(ah > -1 && ah < H && aw > -1 && aw < W)) return 0; /* (a NaN is outside too) */
     int hl = (int)floor((double)ah), wl = (int)floor((double)aw);
     int hh = hl + 1, wh = wl + 1;
     T wt = 0;
@@ -63,7 +63,7 @@ static T FN(grad_weight_corner)(T ah, T aw, int h, int w, int H, int W)
 /* _kernel.cu:144-187 (get_coordinate_weight) / :525-567 (dmcn_get_coordinate_weight). */
 static T FN(coord_weight)(T ah, T aw, int H, int W, const T *plane, int dir)
 {
-    if (ah <= -1 || ah >= H || aw <= -1 || aw >= W) return 0;
+    if (!(ah > -1 && ah < H && aw > -1 && aw < W)) return 0; /* (a NaN is outside too) */
     int hl = (int)floor((double)ah), wl = (int)floor((double)aw);
     int hh = hl + 1, wh = wl + 1;
     T wt = 0;
@@ -211,7 +211,7 @@ int FN(dcn_oracle_backward_input)(const T *x, const T *offset, const T *mask, co
                     T inv_h = (T)(ho * sH - pH + i * dH) + off_h;
                     T inv_w = (T)(wo * sW - pW + j * dW) + off_w;
                     int inside = 1;
-                    if (inv_h <= -1 || inv_w <= -1 || inv_h >= H || inv_w >= W) {
+                    if (!(inv_h > -1 && inv_w > -1 && inv_h < H && inv_w < W)) { /* (a NaN is outside too) */
                         inv_h = inv_w = -2;
                         inside = 0;
                     }
@@ -253,6 +253,10 @@ int FN(dcn_oracle_backward_input)(const T *x, const T *offset, const T *mask, co
                         const T iw = (T)(wo * sW - pW + j * dW) + off_w;
                         T top = gcols[(((long)c * K + k) * N + n) * P + p];
                         if (mp) top = top * mp[(long)k * P + p];
+                        /* A position outside (-1, size) is at least 1 away from every cell, so the scan
+                         * below adds nothing for it; gate before the conversion, which is undefined for
+                         * a NaN, an infinity or a position beyond int. */
+                        if (!(ih > -1 && iw > -1 && ih < H && iw < W)) continue;
                         const int ch = (int)ih, cw = (int)iw;
                         for (int dy = -2; dy <= 2; ++dy)
                             for (int dx = -2; dx <= 2; ++dx) {
