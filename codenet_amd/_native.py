@@ -163,6 +163,11 @@ _SIGNATURES = {
     "cdn_jpeg_workspace_bytes": (ctypes.c_size_t, [_i64] * 3),
     "cdn_jpeg_decode": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp]),
     "cdn_jpeg_decode_host": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i]),
+    "cdn_jpeg_parallel_workspace_bytes": (ctypes.c_size_t, [_i64] * 3),
+    "cdn_jpeg_decode_parallel": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp,
+                                      ctypes.c_size_t, _i, _vp]),
+    "cdn_jpeg_decode_parallel_host": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i, _vp,
+                                           ctypes.c_size_t, _i]),
     "cdn_ctdet_loss_workspace_bytes": (ctypes.c_size_t, [_i64] * 5 + [_i]),
     "cdn_ctdet_loss_forward": (_i, [_vp] * 8 + [_i64] * 5 + [_i] * 3 + [_f] * 3 + [_vp] * 3 + [ctypes.c_size_t, _vp]),
     "cdn_ctdet_loss_backward": (_i, [_vp] * 8 + [_i64] * 5 + [_i] * 2 + [_f] * 3 + [_vp] * 6),

@@ -2,8 +2,9 @@
 // Plain C++ with no HIP call: the host half (header parse, byte packing, decode tables) and the decoder core (bit reader,
 // Huffman lookup, one MCU's blocks, the two IDCT passes, fancy up-sampling and colour).  The core is __host__ __device__
 // under hipcc: jpeg_entropy_idct_kernel / jpeg_color_kernel (codenet_jpeg.hip) and cdn_jpeg_decode_host run the SAME
-// text, the kernel with 64 lanes and a barrier, the host with one lane and none.  tools/probes/jpeg_host_fuzz.cpp
-// includes this file alone.
+// text, the kernel with 64 lanes and a barrier, the host with one lane and none.  The parallel entropy path
+// (decode_segment_parallel: a segment on the 256 lanes of a workgroup; jpeg_entropy_parallel_kernel / jpeg_idct_kernel and
+// cdn_jpeg_decode_parallel_host) follows the same rule.  tools/probes/jpeg_host_fuzz.cpp includes this file alone.
 //
 // The target is equality with libjpeg-turbo's default decode (ISLOW IDCT, fancy up-sampling, 16-bit fixed-point colour).
 // Everything is integer.  Sums and products of the IDCT are formed in uint32_t: for every stream a conforming encoder
@@ -463,6 +464,22 @@ CDN_JPEG_HD void color_pair(const Geom &g, const uint8_t *planes, uint8_t *out, 
   if (two) store_pixel(o + 3, y1, c1[0], c1[1], rgb);
 }
 
+// planes -> interleaved pixels of every item, on one thread
+inline void color_host(const Call &c) {
+  const int ni = n_items(c);
+  for (int item = 0; item < ni; ++item) {
+    Geom g;
+    if (!item_geom(c.items + (int64_t)item * kItemWords, c.plane_stride, &g) || !out_fits(g, c.out_cap)) {
+      if (c.status[item] < kBadRecord) c.status[item] = kBadRecord;
+      continue;
+    }
+    const uint8_t *planes = c.planes + item * c.plane_stride;
+    const int pw = (g.w + 1) / 2;
+    for (int y = 0; y < g.h; ++y)
+      for (int i = 0; i < pw; ++i) color_pair(g, planes, c.out, y, i, c.rgb);
+  }
+}
+
 // ---- the whole call on one thread: what cdn_jpeg_decode_host runs ---------------------------------------------------------
 inline void decode_host(const Call &c) {
   int tile[6 * 64], ws[6 * 64], flag[2] = {0, 0};
@@ -480,17 +497,330 @@ inline void decode_host(const Call &c) {
     const int st = decode_segment(sg, tab, c.planes + sg.item * c.plane_stride, tile, ws, win, flag, 0, 1, NoSync());
     if (st > c.status[sg.item]) c.status[sg.item] = st;
   }
-  for (int item = 0; item < ni; ++item) {
-    Geom g;
-    if (!item_geom(c.items + (int64_t)item * kItemWords, c.plane_stride, &g) || !out_fits(g, c.out_cap)) {
-      if (c.status[item] < kBadRecord) c.status[item] = kBadRecord;
+  color_host(c);
+}
+
+// ==== the parallel entropy path: one segment on the lanes of a workgroup ==================================================
+// The host removed the byte stuffing, so a segment is a plain bit string: it is cut into sub-sequences of S bits, W of
+// them form a tile, and lane j of the workgroup decodes sub-sequence j of the tile.  The decoder state at a bit position is
+// (p, b, z): p the position, b the block within the MCU (it selects the tables), z the zig-zag position (0: a DC symbol
+// is next); DC prediction is NOT part of it, the entropy pass stores DC differences.  A state can also be dead: a bad code
+// was met or the bits ran out.  Per tile: a dry pass from a cold state (p = start of the sub-sequence, 0, 0; lane 0 has
+// the exact state the tile before it left), counted rounds in which lane j decodes again from the exit of lane j - 1
+// whenever that differs from the entry it used last (after round r lanes 0..r are exact by induction, so W - 1 rounds
+// always suffice; Huffman streams self-synchronise, so two or three usually do), an exclusive prefix sum of the blocks
+// each lane completed, and a write pass that stores raw coefficients (int16, natural order, at block * 64 + n) and DC
+// differences (a word per block) into the item's workspace.  After the last tile the DC differences become predictions
+// (an inclusive scan per component) and the status follows from the exact chain alone.  Every loop is counted: a symbol
+// consumes at least one bit, so a sub-sequence decode runs at most S times, and a block index at or beyond count * nblk
+// stores nothing -- that is the bounds check.
+constexpr int kParLanes = 256;                        // W: lanes of the workgroup = sub-sequences of a tile
+constexpr int kParWindow = kParLanes * 128 + 64;      // bytes of a tile of 1024-bit sub-sequences, and its look-ahead
+constexpr int kParMaxLen = (1 << 28) - (1 << 19);     // 8 len + W S + 64 stays below 2^31: bit positions are ints
+static_assert(kParLanes == 256, "par_scan: an even number of doubling steps leaves the sums in place");
+
+CDN_JPEG_HD bool subseq_bits_ok(int s) { return s >= 64 && s <= 8192 && s % 32 == 0; }
+// per item: blocks the planes can hold, their coefficients (64 int16) and DC words
+CDN_JPEG_HD int64_t par_blocks(int64_t plane_stride_) { return plane_stride_ / 64; }
+CDN_JPEG_HD int64_t par_work_stride(int64_t plane_stride_) { return (par_blocks(plane_stride_) * 132 + 15) / 16 * 16; }
+
+struct alignas(16) Coef8 {          // one row of a block's coefficients
+  int16_t v[8];
+};
+struct ParCall {
+  Call c;
+  uint8_t *work;                    // per item: int16 coef[blocks][64], then int32 dc[blocks]
+  int64_t work_stride;
+  int subseq_bits;
+};
+CDN_JPEG_HD int16_t *par_coef(const ParCall &pc, int item) {
+  return reinterpret_cast<int16_t *>(pc.work + (int64_t)item * pc.work_stride);
+}
+CDN_JPEG_HD int32_t *par_dc(const ParCall &pc, int item) {
+  return reinterpret_cast<int32_t *>(pc.work + (int64_t)item * pc.work_stride + par_blocks(pc.c.plane_stride) * 128);
+}
+
+typedef uint64_t PState;            // p << 32 | why << 16 | b << 8 | z; why != 0: dead, and nothing else is set
+CDN_JPEG_HD PState ps_make(int p, int b, int z) { return ((uint64_t)(uint32_t)p << 32) | ((uint32_t)b << 8) | (uint32_t)z; }
+CDN_JPEG_HD PState ps_dead(int why) { return (uint64_t)why << 16; }
+CDN_JPEG_HD int ps_why(PState s) { return (int)(s >> 16) & 3; }
+
+// 32 more bits at any byte position: zeros beyond the segment, and pos always moves on, so the bit position of the next
+// unread bit is 8 pos - n
+CDN_JPEG_HD void par_fill(Bits *b) {
+  if (b->n > 32) return;
+  uint32_t v = 0;
+  const int pos = b->pos;
+  if (pos >= b->wbase && pos + 4 <= b->wend) {      // (the window holds zeros beyond the segment)
+    v = load_be32(b->win + (pos - b->wbase));
+  } else if (pos + 4 <= b->len) {
+    v = load_be32(b->p + pos);
+  } else {
+    for (int i = 0; i < 4; ++i)
+      if (pos + i < b->len) v |= (uint32_t)b->p[pos + i] << (24 - 8 * i);
+  }
+  b->pos = pos + 4;
+  b->acc |= (uint64_t)v << (32 - b->n);
+  b->n += 32;
+}
+
+// what a sub-sequence decode needs beside its entry state
+struct ParSeg {
+  Bits src;                         // bytes, length and window of the segment
+  const Tables *tab;
+  int sel, ncomp, nblk;
+  int total_bits;                   // 8 len
+  int limit;                        // count * nblk: blocks of the segment
+  int16_t *coef;                    // of the segment's first block
+  int32_t *dc;
+};
+
+// The symbols that START in [p of entry, end).  -> the exit state: that of the first symbol start at or beyond `end`, or
+// dead; *done = blocks completed (EOB or k reaching 64).  An entry at or beyond `end`, or a dead one, is its own exit.
+// kStore: coefficients and DC differences of blocks below the limit are stored, `blk` being the block the entry lies in.
+template <bool kStore>
+CDN_JPEG_HD PState par_subseq(const ParSeg &ps, PState entry, int end, int blk, int *done) {
+  *done = 0;
+  if (ps_why(entry)) return entry;
+  int p = (int)(entry >> 32), b = (int)(entry >> 8) & 7, z = (int)entry & 127;
+  if (p >= end) return entry;
+  Bits br = ps.src;
+  br.pos = p >> 3;
+  br.acc = 0;
+  br.n = 0;
+  br.real = 0;
+  par_fill(&br);
+  bits_skip(&br, p & 7);
+  int n = 0;
+  while (p < end) {                 // p grows by at least 1 per iteration
+    if (kStore && blk >= ps.limit) break;
+    par_fill(&br);
+    const int comp = ps.ncomp == 1 ? 0 : (b < ps.nblk - 2 ? 0 : b - (ps.nblk - 2) + 1);
+    const Huff *t = &ps.tab->huff[z == 0 ? (ps.sel >> (2 * comp)) & 1 : 2 + ((ps.sel >> (2 * comp + 1)) & 1)];
+    const int sym = huff_symbol(&br, t);
+    if (sym < 0) {                  // with real bits in all 16 places it is a bad code; otherwise the bits ran out
+      *done = n;
+      return ps_dead(p + 16 > ps.total_bits ? kOverread : kBadCode);
+    }
+    const int tb = sym & 15;
+    const int v = tb ? receive_extend(&br, tb) : 0;        // (<= 16 + 15 bits since the fill)
+    const int q = 8 * br.pos - br.n;                       // where the next symbol starts
+    if (q > ps.total_bits) {        // the symbol needed bits beyond the end
+      *done = n;
+      return ps_dead(kOverread);
+    }
+    p = q;
+    if (z == 0) {
+      if (kStore) ps.dc[blk] = v;
+      z = 1;
+    } else if (tb) {
+      z += sym >> 4;
+      if (kStore && z < 64) ps.coef[(int64_t)blk * 64 + (ps.tab->zigzag[z] & 63)] = (int16_t)v;
+      z += 1;
+    } else if ((sym >> 4) == 15) {
+      z += 16;                      // ZRL
+    } else {
+      z = 64;                       // EOB
+    }
+    if (z >= 64) {
+      ++n;
+      ++blk;
+      b = b + 1 == ps.nblk ? 0 : b + 1;
+      z = 0;
+    }
+  }
+  *done = n;
+  return ps_make(p, b, z);
+}
+
+// inclusive sums (uint32 wrap-around) of a[0 .. W) in place; tmp: W more words.  The caller's last sync() is behind the
+// writes of a.
+template <class Sync>
+CDN_JPEG_HD void par_scan(uint32_t *a, uint32_t *tmp, int lane, int nlanes, Sync sync) {
+  uint32_t *src = a, *dst = tmp;
+  for (int d = 1; d < kParLanes; d <<= 1) {
+    for (int j = lane; j < kParLanes; j += nlanes) dst[j] = src[j] + (j >= d ? src[j - d] : 0u);
+    sync();
+    uint32_t *t = src;
+    src = dst;
+    dst = t;
+  }
+}
+
+// the workgroup's shared arrays (LDS on the device)
+struct ParShared {
+  PState *exit;                     // [2][W]: the exits of the round before and of this round
+  PState *entry;                    // [W]: the entry each lane used last
+  int *cnt;                         // [W]: blocks each lane completed
+  uint32_t *scan;                   // [4][W]
+  int *flag;                        // [3]: "an exit changed" of rounds r % 3
+  uint8_t *win;                     // [kParWindow]: the tile's bytes
+};
+
+// One segment.  `lane` of `nlanes` callers run this together (the kernel: the W lanes of a workgroup; the host: one, which
+// takes every j in turn); sync() is a barrier that every caller reaches the same number of times -- the conditions around
+// it depend on the segment record and on words all callers read behind a sync() alone.  -> the status, the same in every
+// caller.
+template <class Sync>
+CDN_JPEG_HD int decode_segment_parallel(const Segment &sg, const Tables *tab, int16_t *item_coef, int32_t *item_dc, int S,
+                                        const ParShared &sh, int lane, int nlanes, Sync sync) {
+  constexpr int W = kParLanes;
+  const Geom &g = sg.g;
+  if (sg.len > kParMaxLen) return kBadRecord;
+  ParSeg ps;
+  bits_init(&ps.src, sg.bytes, sg.len);
+  ps.src.win = sh.win;
+  ps.tab = tab;
+  ps.sel = g.sel;
+  ps.ncomp = g.ncomp;
+  ps.nblk = g.ncomp == 1 ? 1 : g.hs * g.vs + 2;          // <= 6
+  ps.total_bits = 8 * sg.len;
+  ps.limit = sg.count * ps.nblk;
+  ps.coef = item_coef + (int64_t)sg.first * ps.nblk * 64;
+  ps.dc = item_dc + (int64_t)sg.first * ps.nblk;
+  // the segment's blocks start as zeros: what the image needs, not the capacity (a block is 8 rows of 16 bytes, and the
+  // workspace is 16-byte aligned)
+  Coef8 *clear = reinterpret_cast<Coef8 *>(ps.coef);
+  for (int64_t i = lane; i < (int64_t)ps.limit * 8; i += nlanes) clear[i] = Coef8{{0, 0, 0, 0, 0, 0, 0, 0}};
+  for (int i = lane; i < ps.limit; i += nlanes) ps.dc[i] = 0;
+  sync();
+  const int nsub = (ps.total_bits + S - 1) / S, ntiles = (nsub + W - 1) / W;
+  PState carry = ps_make(0, 0, 0);
+  int carry_blk = 0;
+  for (int t = 0; t < ntiles; ++t) {
+    const int sub0 = t * W;
+    // the tile's bytes and 64 of look-ahead, zeros beyond the segment
+    const int wbase = sub0 * (S / 8), avail = sg.len - wbase, tile_bytes = W * (S / 8);
+    int wn = (avail < tile_bytes ? avail : tile_bytes) + 64;
+    wn = wn < kParWindow ? wn : kParWindow;
+    for (int i = lane; i < wn; i += nlanes) sh.win[i] = wbase + i < sg.len ? sg.bytes[wbase + i] : (uint8_t)0;
+    if (lane == 0) sh.flag[1] = 0;
+    sync();
+    ps.src.wbase = wbase;
+    ps.src.wend = wbase + wn;
+    // dry pass: lane 0 from the exact state, every other lane cold; na: the sub-sequences of this tile -- the lanes that
+    // take part (a lane beyond them completes no block)
+    const int na = nsub - sub0 < W ? nsub - sub0 : W;
+    for (int j = lane; j < W; j += nlanes) {
+      const int start = (sub0 + j) * S;
+      int n = 0;
+      if (j < na) {
+        sh.entry[j] = j == 0 ? carry : ps_make(start, 0, 0);
+        sh.exit[j] = par_subseq<false>(ps, sh.entry[j], start + S, 0, &n);
+      }
+      sh.cnt[j] = n;
+    }
+    sync();
+    // synchronisation rounds: after round r the lanes 0 .. r are exact, so na - 1 rounds always suffice
+    int cur = 0;
+    for (int r = 1; r < na; ++r) {
+      const PState *prev = sh.exit + cur * W;
+      cur ^= 1;
+      PState *next = sh.exit + cur * W;
+      for (int j = lane; j < na; j += nlanes) {
+        PState x = prev[j];
+        if (j > 0 && prev[j - 1] != sh.entry[j]) {
+          int n;
+          sh.entry[j] = prev[j - 1];
+          const PState y = par_subseq<false>(ps, sh.entry[j], (sub0 + j + 1) * S, 0, &n);
+          sh.cnt[j] = n;
+          if (y != x) sh.flag[r % 3] = 1;
+          x = y;
+        }
+        next[j] = x;
+      }
+      if (lane == 0) sh.flag[(r + 1) % 3] = 0;
+      sync();
+      if (!sh.flag[r % 3]) break;   // (uniform: every caller reads the word behind the same sync)
+    }
+    // block indices: exclusive prefix sum of the counts
+    for (int j = lane; j < W; j += nlanes) sh.scan[j] = (uint32_t)sh.cnt[j];
+    sync();
+    par_scan(sh.scan, sh.scan + W, lane, nlanes, sync);
+    // write pass
+    for (int j = lane; j < na; j += nlanes) {
+      int n;
+      par_subseq<true>(ps, sh.entry[j], (sub0 + j + 1) * S, carry_blk + (int)sh.scan[j] - sh.cnt[j], &n);
+    }
+    carry = sh.exit[cur * W + na - 1];
+    carry_blk += (int)sh.scan[W - 1];
+    sync();
+  }
+  // DC differences -> predictions: lane j takes MCUs [j per, (j + 1) per)
+  const int per = (sg.count + W - 1) / W;
+  for (int j = lane; j < W; j += nlanes) {
+    uint32_t sum[3] = {0, 0, 0};
+    for (int m = j * per; m < (j + 1) * per && m < sg.count; ++m)
+      for (int b = 0; b < ps.nblk; ++b)
+        sum[ps.ncomp == 1 || b < ps.nblk - 2 ? 0 : b - (ps.nblk - 2) + 1] += (uint32_t)ps.dc[m * ps.nblk + b];
+    for (int c = 0; c < 3; ++c) sh.scan[c * W + j] = sum[c];
+  }
+  sync();
+  for (int c = 0; c < ps.ncomp; ++c) par_scan(sh.scan + c * W, sh.scan + 3 * W, lane, nlanes, sync);
+  for (int j = lane; j < W; j += nlanes) {
+    uint32_t pred[3];
+    for (int c = 0; c < 3; ++c) pred[c] = j > 0 ? sh.scan[c * W + j - 1] : 0u;
+    for (int m = j * per; m < (j + 1) * per && m < sg.count; ++m)
+      for (int b = 0; b < ps.nblk; ++b) {
+        const int c = ps.ncomp == 1 || b < ps.nblk - 2 ? 0 : b - (ps.nblk - 2) + 1;
+        pred[c] += (uint32_t)ps.dc[m * ps.nblk + b];
+        ps.dc[m * ps.nblk + b] = (int32_t)pred[c];
+      }
+  }
+  sync();
+  // the exact chain alone decides: complete, or why it stopped short
+  return carry_blk >= ps.limit ? 0 : (ps_why(carry) == kBadCode ? kBadCode : kOverread);
+}
+
+// block `blk` of an item (MCU-interleaved order): coefficient row r, dequantised, into tile[r * 8 ..]
+CDN_JPEG_HD void par_dequant_row(const int16_t *coef, const int32_t *dc, int64_t blk, const uint8_t *q, int r, int *tile) {
+  const Coef8 c8 = *reinterpret_cast<const Coef8 *>(coef + blk * 64 + r * 8);
+  for (int x = 0; x < 8; ++x) tile[r * 8 + x] = (int)((uint32_t)(int)c8.v[x] * (uint32_t)q[r * 8 + x]);
+  if (r == 0) tile[0] = (int)((uint32_t)dc[blk] * (uint32_t)q[0]);
+}
+CDN_JPEG_HD int block_comp(const Geom &g, int b) {
+  const int ny = g.hs * g.vs;
+  return g.ncomp == 1 || b < ny ? 0 : 1 + (b - ny);
+}
+
+// ---- the whole parallel call on one thread: what cdn_jpeg_decode_parallel_host runs ---------------------------------------
+inline void decode_host_parallel(const ParCall &pc) {
+  const Call &c = pc.c;
+  PState exit_[2 * kParLanes], entry[kParLanes];
+  int cnt[kParLanes], flag[3] = {0, 0, 0};
+  uint32_t scan[4 * kParLanes];
+  uint8_t win[kParWindow];
+  const ParShared sh{exit_, entry, cnt, scan, flag, win};
+  const int ns = n_segments(c), ni = n_items(c);
+  for (int s = 0; s < ns; ++s) {
+    Segment sg;
+    if (!segment_geom(c, s, &sg)) {
+      const int item = c.segs[(int64_t)(1 + s) * kSegWords + kSegItem];
+      if (item >= 0 && item < ni && c.status[item] < kBadRecord) c.status[item] = kBadRecord;
       continue;
     }
-    const uint8_t *planes = c.planes + item * c.plane_stride;
-    const int pw = (g.w + 1) / 2;
-    for (int y = 0; y < g.h; ++y)
-      for (int i = 0; i < pw; ++i) color_pair(g, planes, c.out, y, i, c.rgb);
+    const Tables *tab = reinterpret_cast<const Tables *>(c.tables + (int64_t)sg.item * kTableBytes);
+    const int st = decode_segment_parallel(sg, tab, par_coef(pc, sg.item), par_dc(pc, sg.item), pc.subseq_bits, sh, 0, 1,
+                                           NoSync());
+    if (st > c.status[sg.item]) c.status[sg.item] = st;
   }
+  for (int item = 0; item < ni; ++item) {
+    Geom g;
+    if (!item_geom(c.items + (int64_t)item * kItemWords, c.plane_stride, &g)) continue;      // (color_host sets the status)
+    const Tables *tab = reinterpret_cast<const Tables *>(c.tables + (int64_t)item * kTableBytes);
+    const int nblk = g.ncomp == 1 ? 1 : g.hs * g.vs + 2;
+    const int64_t total = (int64_t)g.mcus_x * g.mcus_y * nblk;
+    int tile[64], ws[64];
+    for (int64_t blk = 0; blk < total; ++blk) {
+      const int mi = (int)(blk / nblk), b = (int)(blk - (int64_t)mi * nblk), my = mi / g.mcus_x, mx = mi - my * g.mcus_x;
+      int comp, pitch;
+      uint8_t *o = block_origin(g, c.planes + item * c.plane_stride, mx, my, b, &comp, &pitch);
+      for (int r = 0; r < 8; ++r) par_dequant_row(par_coef(pc, item), par_dc(pc, item), blk, tab->quant[comp], r, tile);
+      for (int col = 0; col < 8; ++col) idct_column(tile, ws, col);
+      for (int r = 0; r < 8; ++r) store8(o + (int64_t)r * pitch, idct_row(ws, r));
+    }
+  }
+  color_host(c);
 }
 
 // ==== host half: header parse, decode tables, byte packing ================================================================

@@ -72,7 +72,85 @@ __global__ void __launch_bounds__(kColorThreads) jpeg_color_kernel(J::Call c) {
   }
 }
 
-int make_call(J::Call *c, const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs, int64_t seg_cap,
+// ---- the parallel entropy path (cdn_jpeg_decode_parallel): three launches --------------------------------------------------
+// jpeg_entropy_parallel_kernel: a workgroup of W = 256 lanes per segment, striding over the records like the kernel above.
+//   The segment's bits are cut into sub-sequences of subseq_bits, 256 to a tile; the tile's bytes go to an LDS window and
+//   J::decode_segment_parallel runs the dry pass, the counted synchronisation rounds, the prefix sum and the write pass
+//   on them; raw coefficients and DC words go to the item's workspace.  Every barrier is reached by every lane.
+// jpeg_idct_kernel: all blocks of all items, 32 to a workgroup step (8 lanes a block), grid-stride with a grid from the
+//   capacities: dequantise, the two IDCT passes through LDS, rows of 8 samples to the planes.
+// jpeg_color_kernel, unchanged.
+constexpr int kIdctBlocks = 32;     // blocks per workgroup step of jpeg_idct_kernel
+
+struct GroupSync {
+  __device__ __forceinline__ void operator()() const { __syncthreads(); }      // the four waves of the workgroup
+};
+
+__global__ void __launch_bounds__(J::kParLanes) jpeg_entropy_parallel_kernel(J::ParCall pc) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[J::kTableBytes / 4];
+  __shared__ J::PState s_exit[2 * J::kParLanes], s_entry[J::kParLanes];
+  __shared__ int s_cnt[J::kParLanes], s_flag[3];
+  __shared__ uint32_t s_scan[4 * J::kParLanes];
+  __shared__ uint8_t s_win[J::kParWindow];
+  const J::Call &c = pc.c;
+  const J::ParShared sh{s_exit, s_entry, s_cnt, s_scan, s_flag, s_win};
+  const int lane = threadIdx.x;
+  int loaded = -1;
+  const int ns = J::n_segments(c), ni = J::n_items(c);
+  for (int s = blockIdx.x; s < ns; s += gridDim.x) {
+    J::Segment sg;
+    if (!J::segment_geom(c, s, &sg)) {          // (the same answer in every lane)
+      const int item = c.segs[(int64_t)(1 + s) * J::kSegWords + J::kSegItem];
+      if (lane == 0 && item >= 0 && item < ni) atomicMax(c.status + item, (int)J::kBadRecord);
+      continue;
+    }
+    if (sg.item != loaded) {
+      __syncthreads();
+      const uint32_t *src = reinterpret_cast<const uint32_t *>(c.tables + (int64_t)sg.item * J::kTableBytes);
+      for (int k = lane; k < J::kTableBytes / 4; k += J::kParLanes) s_tab[k] = src[k];
+      loaded = sg.item;
+    }
+    __syncthreads();
+    const int st = J::decode_segment_parallel(sg, reinterpret_cast<const J::Tables *>(s_tab), J::par_coef(pc, sg.item),
+                                              J::par_dc(pc, sg.item), pc.subseq_bits, sh, lane, J::kParLanes, GroupSync());
+    if (st && lane == 0) atomicMax(c.status + sg.item, st);
+  }
+}
+
+__global__ void __launch_bounds__(kIdctBlocks * 8) jpeg_idct_kernel(J::ParCall pc) {
+  __shared__ int s_tile[kIdctBlocks * 64], s_ws[kIdctBlocks * 64];
+  const J::Call &c = pc.c;
+  const int64_t steps_per_item = (J::par_blocks(c.plane_stride) + kIdctBlocks - 1) / kIdctBlocks;
+  const int64_t steps = steps_per_item * J::n_items(c);
+  const int lb = threadIdx.x >> 3, l = threadIdx.x & 7;
+  for (int64_t step = blockIdx.x; step < steps; step += gridDim.x) {      // (item, geometry and `first`: the same in every lane)
+    const int item = (int)(step / steps_per_item);
+    const int64_t first = (step - item * steps_per_item) * kIdctBlocks;
+    J::Geom g;
+    if (!J::item_geom(c.items + (int64_t)item * J::kItemWords, c.plane_stride, &g)) continue;      // (the colour kernel flags it)
+    const int nblk = g.ncomp == 1 ? 1 : g.hs * g.vs + 2;
+    const int64_t total = (int64_t)g.mcus_x * g.mcus_y * nblk;
+    if (first >= total) continue;
+    const int64_t blk = first + lb;
+    const bool valid = blk < total;
+    const int mi = (int)(blk / nblk), b = (int)(blk - (int64_t)mi * nblk), my = mi / g.mcus_x, mx = mi - my * g.mcus_x;
+    int *tile = s_tile + lb * 64, *ws = s_ws + lb * 64;
+    if (valid) {
+      const J::Tables *tab = reinterpret_cast<const J::Tables *>(c.tables + (int64_t)item * J::kTableBytes);
+      J::par_dequant_row(J::par_coef(pc, item), J::par_dc(pc, item), blk, tab->quant[J::block_comp(g, b)], l, tile);
+    }
+    __syncthreads();
+    if (valid) J::idct_column(tile, ws, l);
+    __syncthreads();
+    if (valid) {
+      int comp, pitch;
+      uint8_t *o = J::block_origin(g, c.planes + item * c.plane_stride, mx, my, b, &comp, &pitch);
+      J::store8(o + (int64_t)l * pitch, J::idct_row(ws, l));
+    }
+  }
+}
+
+int make_call(J::Call *c,const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs, int64_t seg_cap,
               const int32_t *items, int64_t item_cap, const unsigned char *tables, unsigned char *planes,
               int64_t plane_stride, int32_t *status, unsigned char *out, int64_t out_cap, int rgb) {
   CDN_REQUIRE(stream_bytes && segs && items && tables && planes && status && out, CDN_ERR_ARG, "null pointer");
@@ -161,5 +239,73 @@ extern "C" int cdn_jpeg_decode(const unsigned char *stream_bytes, int64_t stream
   int64_t gx = cdn::ceil_div(cap_pairs, kColorThreads);
   gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
   jpeg_color_kernel<<<dim3((unsigned)gx, (unsigned)item_cap), kColorThreads, 0, st>>>(c);
+  return cdn::check_launch("jpeg color");
+}
+
+// ---- the parallel entropy path ---------------------------------------------------------------------------------------------
+namespace {
+
+int make_par_call(J::ParCall *pc, unsigned char *workspace, size_t workspace_bytes, int subseq_bits) {
+  CDN_REQUIRE(workspace, CDN_ERR_ARG, "null pointer");
+  CDN_REQUIRE(J::subseq_bits_ok(subseq_bits), CDN_ERR_ARG, "subseq_bits must be a multiple of 32 in 64..8192, got %d",
+              subseq_bits);
+  const int64_t stride = J::par_work_stride(pc->c.plane_stride);
+  CDN_REQUIRE(stride > 0, CDN_ERR_ARG, "a plane stride below the 64 bytes of one block");
+  CDN_REQUIRE(cdn::aligned16(workspace) &&workspace_bytes / (size_t)stride >= (size_t)pc->c.item_cap, CDN_ERR_ARG,
+              "the coefficient workspace must be 16-byte aligned and hold %lld bytes per item", (long long)stride);
+  pc->work = workspace;
+  pc->work_stride = stride;
+  pc->subseq_bits = subseq_bits;
+  return CDN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t cdn_jpeg_parallel_workspace_bytes(int64_t max_items, int64_t max_h, int64_t max_w) {
+  if (max_items < 1 || max_h < 1 || max_w < 1 || max_h > 65535 || max_w > 65535) return 0;
+  return (size_t)max_items * (size_t)J::par_work_stride(J::plane_stride(max_h, max_w));
+}
+
+extern "C" int cdn_jpeg_decode_parallel_host(const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs,
+                                             int64_t seg_cap, const int32_t *items, int64_t item_cap,
+                                             const unsigned char *tables, unsigned char *planes, int64_t plane_stride,
+                                             int32_t *status, unsigned char *out, int64_t out_cap, int rgb,
+                                             unsigned char *workspace, size_t workspace_bytes, int subseq_bits) {
+  J::ParCall pc;
+  int rc = make_call(&pc.c, stream_bytes, stream_cap, segs, seg_cap, items, item_cap, tables, planes, plane_stride, status, out,
+                     out_cap, rgb);
+  if (rc != CDN_OK) return rc;
+  rc = make_par_call(&pc, workspace, workspace_bytes, subseq_bits);
+  if (rc != CDN_OK) return rc;
+  J::decode_host_parallel(pc);
+  return CDN_OK;
+}
+
+extern "C" int cdn_jpeg_decode_parallel(const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs,
+                                        int64_t seg_cap, const int32_t *items, int64_t item_cap, const unsigned char *tables,
+                                        unsigned char *planes, int64_t plane_stride, int32_t *status, unsigned char *out,
+                                        int64_t out_cap, int rgb, unsigned char *workspace, size_t workspace_bytes,
+                                        int subseq_bits, void *stream) {
+  J::ParCall pc;
+  int rc = make_call(&pc.c, stream_bytes, stream_cap, segs, seg_cap, items, item_cap, tables, planes, plane_stride, status, out,
+                     out_cap, rgb);
+  if (rc != CDN_OK) return rc;
+  rc = make_par_call(&pc, workspace, workspace_bytes, subseq_bits);
+  if (rc != CDN_OK) return rc;
+  hipStream_t st = cdn::as_stream(stream);
+  // the three grids from the capacities: the counts of this batch are device words
+  const unsigned eg = (unsigned)(seg_cap < 4096 ? seg_cap : 4096);
+  jpeg_entropy_parallel_kernel<<<eg, J::kParLanes, 0, st>>>(pc);
+  rc = cdn::check_launch("jpeg entropy_parallel");
+  if (rc != CDN_OK) return rc;
+  int64_t ig = cdn::ceil_div(J::par_blocks(plane_stride), kIdctBlocks) * item_cap;
+  ig = ig < 1 ? 1 : (ig > 16384 ? 16384 : ig);
+  jpeg_idct_kernel<<<(unsigned)ig, kIdctBlocks * 8, 0, st>>>(pc);
+  rc = cdn::check_launch("jpeg idct");
+  if (rc != CDN_OK) return rc;
+  const int64_t cap_pairs = plane_stride / 6;                     // pixel pairs of the largest item the planes hold
+  int64_t gx = cdn::ceil_div(cap_pairs, kColorThreads);
+  gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
+  jpeg_color_kernel<<<dim3((unsigned)gx, (unsigned)item_cap), kColorThreads, 0, st>>>(pc.c);
   return cdn::check_launch("jpeg color");
 }

@@ -11,9 +11,18 @@ Supported: SOF0 (baseline), 8-bit samples and quantisation tables, one interleav
 before anything is copied, so a caller can fall back to a decoder of its own.
 
 The host parses the header and, in one pass, removes the byte stuffing and cuts the entropy-coded bytes at the restart
-markers into segments; the GPU does the rest in two launches.  A segment is a dependent chain that ONE lane decodes: the
-entropy kernel's concurrency is batch size x restart intervals.  Files without restart markers (Pascal VOC) give one
-segment per image, so the batch is the only parallelism of that kernel.
+markers into segments; the GPU does the rest.  Two entropy paths write the same pixels:
+
+entropy="serial" (the default, two launches): a segment is a dependent chain that ONE lane decodes, so the entropy
+kernel's concurrency is batch size x restart intervals.  Files without restart markers (Pascal VOC) give one segment per
+image, and the batch is the only parallelism of that kernel.
+
+entropy="parallel" (three launches): a segment is decoded by the 256 lanes of a workgroup.  Without its stuffing a segment
+is a plain bit string; it is cut into sub-sequences of subseq_bits bits, every lane decodes one from a guessed state, and
+counted rounds hand the exact state from lane to lane until nothing changes (255 rounds always suffice; Huffman streams
+self-synchronise, so far fewer can -- but the block position within the MCU does not).  It needs a
+coefficient workspace of 2.0625 x the plane bytes (6.19 MiB per item at the 1024 x 1024 default, 1.16 MiB at 375 x 500).
+DESIGN.md section 7.4d has the algorithm and the measurements.
 """
 import collections
 
@@ -91,12 +100,25 @@ def _pack(datas, layout, stream, segs, items, tables, plane_stride):
     return int(used[0]), int(used[1])
 
 
-def decode_host_raw(datas, order="bgr", guard=0):
-    """The whole decode on the calling thread through cdn_jpeg_decode_host -- the text the kernels run -- without a GPU.
+ENTROPY = ("serial", "parallel")
+
+
+def _check_entropy(entropy, subseq_bits):
+    if entropy not in ENTROPY:
+        raise ValueError("entropy must be 'serial' or 'parallel'")
+    if entropy == "parallel" and not (64 <= int(subseq_bits) <= 8192 and int(subseq_bits) % 32 == 0):
+        raise ValueError("subseq_bits must be a multiple of 32 in 64..8192")
+
+
+def decode_host_raw(datas, order="bgr", guard=0, entropy="serial", subseq_bits=1024):
+    """The whole decode on the calling thread through cdn_jpeg_decode_host (or, with entropy='parallel',
+    cdn_jpeg_decode_parallel_host) -- the text the kernels run -- without a GPU.
     -> dict(infos, layout, out, planes, status, out_buf, planes_buf): out / planes are the views the library was given,
-    *_buf the allocations around them with `guard` bytes of 0xA5 on either side."""
+    *_buf the allocations around them with `guard` bytes of 0xA5 on either side; the parallel path adds work / work_buf,
+    its coefficient workspace."""
     if order not in ("bgr", "rgb"):
         raise ValueError("order must be 'bgr' or 'rgb'")
+    _check_entropy(entropy, subseq_bits)
     datas = [_as_bytes(d) for d in datas]
     infos = [parse(d) for d in datas]
     layout, total = default_layout(infos)
@@ -113,12 +135,20 @@ def decode_host_raw(datas, order="bgr", guard=0):
     out_buf[:], planes_buf[:] = 0xA5, 0xA5
     out, planes = out_buf[guard:guard + total], planes_buf[guard:guard + n * stride]
     status = np.zeros(n, dtype=np.int32)
-    rc = lib.cdn_jpeg_decode_host(stream.ctypes.data, stream.size, segs.ctypes.data, nseg, items.ctypes.data, n,
-                                  tables.ctypes.data, planes.ctypes.data, stride, status.ctypes.data, out.ctypes.data,
-                                  total, int(order == "rgb"))
-    N_.check(rc, "cdn_jpeg_decode_host")
-    return {"infos": infos, "layout": layout, "out": out, "planes": planes, "status": status, "out_buf": out_buf,
-            "planes_buf": planes_buf, "guard": guard}
+    r = {"infos": infos, "layout": layout, "out": out, "planes": planes, "status": status, "out_buf": out_buf,
+         "planes_buf": planes_buf, "guard": guard}
+    args = [stream.ctypes.data, stream.size, segs.ctypes.data, nseg, items.ctypes.data, n, tables.ctypes.data,
+            planes.ctypes.data, stride, status.ctypes.data, out.ctypes.data, total, int(order == "rgb")]
+    if entropy == "parallel":
+        nwork = n * max(int(lib.cdn_jpeg_parallel_workspace_bytes(1, i.h, i.w)) for i in infos)       # (of the largest planes)
+        r["work_buf"] = _aligned(nwork + 2 * guard)
+        r["work_buf"][:] = 0xA5
+        r["work"] = r["work_buf"][guard:guard + nwork]
+        rc = lib.cdn_jpeg_decode_parallel_host(*(args + [r["work"].ctypes.data, nwork, int(subseq_bits)]))
+        N_.check(rc, "cdn_jpeg_decode_parallel_host")
+    else:
+        N_.check(lib.cdn_jpeg_decode_host(*args), "cdn_jpeg_decode_host")
+    return r
 
 
 def _raise_status(status):
@@ -128,10 +158,10 @@ def _raise_status(status):
                                                               for k, s in bad))
 
 
-def decode_host(datas, order="bgr"):
-    """[JPEG streams] -> [uint8 h x w x 3 numpy arrays], decoded on the host by the library (no GPU needed).  RuntimeError
-    when an item's entropy-coded data is corrupt."""
-    r = decode_host_raw(datas, order)
+def decode_host(datas, order="bgr", entropy="serial", subseq_bits=1024):
+    """[JPEG streams] -> [uint8 h x w x 3 numpy arrays], decoded on the host by the library (no GPU needed); entropy and
+    subseq_bits as JpegDecoder takes them.  RuntimeError when an item's entropy-coded data is corrupt."""
+    r = decode_host_raw(datas, order, entropy=entropy, subseq_bits=subseq_bits)
     _raise_status(r["status"])
     return [r["out"][off:off + h * w * 3].reshape(h, w, 3).copy() for off, h, w, _ in r["layout"]]
 
@@ -140,14 +170,18 @@ class JpegDecoder:
     """Owns the pinned staging, the device stream / segment / table buffers, the component planes and the status words
     for batches of up to max_items images of up to max_h x max_w.  load(datas) -> run(out_bytes); run is two launches and
     capturable, and because every per-batch value lives in device memory a captured run replays for any batch inside
-    the capacities."""
+    the capacities.  entropy='parallel' decodes a segment on the 256 lanes of a workgroup in sub-sequences of subseq_bits
+    bits (a multiple of 32 in 64..8192): three launches, the same pixels, and a coefficient workspace of 2.0625 x the
+    plane bytes beside the planes."""
 
     decode_host = staticmethod(decode_host)
 
     def __init__(self, max_items=1, max_h=1024, max_w=1024, max_stream_bytes=None, max_segments=None, device="cuda",
-                 order="bgr"):
+                 order="bgr", entropy="serial", subseq_bits=1024):
         if order not in ("bgr", "rgb"):
             raise ValueError("order must be 'bgr' or 'rgb'")
+        _check_entropy(entropy, subseq_bits)
+        self.entropy, self.subseq_bits = entropy, int(subseq_bits)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise NotImplementedError("JpegDecoder needs a GPU device (decode_host() runs without one)")
@@ -168,6 +202,10 @@ class JpegDecoder:
         self._dev = {k: torch.zeros(n, dtype=t, device=self.device) for k, (n, t) in sizes.items()}
         self.planes = torch.zeros(self.max_items * self.plane_stride, dtype=torch.uint8, device=self.device)
         self._status = torch.zeros(self.max_items, dtype=torch.int32, device=self.device)
+        self.work = None
+        if entropy == "parallel":
+            nwork = int(N_.lib().cdn_jpeg_parallel_workspace_bytes(self.max_items, self.max_h, self.max_w))
+            self.work = torch.zeros(nwork, dtype=torch.uint8, device=self.device)
         self.P, self.infos, self.layout, self.out_bytes = 0, [], [], 0
         self._copied = None
 
@@ -199,7 +237,7 @@ class JpegDecoder:
         return infos
 
     def run(self, out_bytes):
-        """The two launches on the current stream: item k's pixels go to out_bytes[offset_k + y pitch_k + 3 x] (layout),
+        """The two launches (three with entropy='parallel') on the current stream: item k's pixels go to out_bytes[offset_k + y pitch_k + 3 x] (layout),
         B G R (or R G B with order='rgb').  out_bytes: a contiguous uint8 GPU tensor of at least self.out_bytes bytes; a
         captured run checks every later batch against its size on the device (status 3)."""
         if not isinstance(out_bytes, torch.Tensor) or not out_bytes.is_cuda:
@@ -211,12 +249,16 @@ class JpegDecoder:
             raise ValueError("out_bytes must be a contiguous uint8 tensor of at least %d bytes on %s"
                              % (self.out_bytes, self.planes.device))
         d = self._dev
-        rc = N_.lib().cdn_jpeg_decode(d["stream"].data_ptr(), self.max_stream_bytes, d["segs"].data_ptr(),
-                                      self.max_segments, d["items"].data_ptr(), self.max_items, d["tables"].data_ptr(),
-                                      self.planes.data_ptr(), self.plane_stride, self._status.data_ptr(),
-                                      out_bytes.data_ptr(), out_bytes.numel(), int(self.rgb),
-                                      torch.cuda.current_stream(self.planes.device).cuda_stream)
-        N_.check(rc, "cdn_jpeg_decode")
+        args = [d["stream"].data_ptr(), self.max_stream_bytes, d["segs"].data_ptr(), self.max_segments,
+                d["items"].data_ptr(), self.max_items, d["tables"].data_ptr(), self.planes.data_ptr(), self.plane_stride,
+                self._status.data_ptr(), out_bytes.data_ptr(), out_bytes.numel(), int(self.rgb)]
+        stream = torch.cuda.current_stream(self.planes.device).cuda_stream
+        if self.work is not None:
+            rc = N_.lib().cdn_jpeg_decode_parallel(*(args + [self.work.data_ptr(), self.work.numel(), self.subseq_bits,
+                                                             stream]))
+            N_.check(rc, "cdn_jpeg_decode_parallel")
+        else:
+            N_.check(N_.lib().cdn_jpeg_decode(*(args + [stream])), "cdn_jpeg_decode")
         return out_bytes
 
     @property

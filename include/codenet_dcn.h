@@ -1051,6 +1051,32 @@ int cdn_jpeg_decode_host(const unsigned char *stream_bytes, int64_t stream_cap, 
                          const int32_t *items, int64_t item_cap, const unsigned char *tables, unsigned char *planes,
                          int64_t plane_stride, int32_t *status, unsigned char *out, int64_t out_cap, int rgb);
 
+/* The parallel entropy path (opt-in; the five functions above are untouched by it).  The same buffers and records, the
+ * same pixels and the same zero / non-zero status as cdn_jpeg_decode, but a segment is decoded by the 256 lanes of a
+ * workgroup: its bits (the host removed the stuffing) are cut into sub-sequences of subseq_bits, every lane decodes one
+ * from a guessed state, and counted rounds hand the exact state from lane to lane.  Files
+ * without restart markers no longer decode as one chain per image.
+ * cdn_jpeg_parallel_workspace_bytes: the raw coefficients (int16 x 64 per 8 x 8 block) and DC words (int32 per block) of
+ *   max_items images: 2.0625 x the plane bytes -- 6.19 MiB per item for the 1024 x 1024 default, 1.16 MiB for 375 x 500.
+ *   0: a size outside 1..65535.
+ * cdn_jpeg_decode_parallel: three launches on `stream`, capturable -- jpeg_entropy_parallel_kernel (segments -> workspace),
+ *   jpeg_idct_kernel (workspace -> planes) and jpeg_color_kernel.  workspace: DEVICE memory, 16-byte aligned, at least
+ *   cdn_jpeg_parallel_workspace_bytes(item_cap, ...) for the plane_stride given; subseq_bits: a multiple of 32 in
+ *   64..8192; anything else is CDN_ERR_ARG.
+ *   status: 0 exactly when cdn_jpeg_decode gives 0; otherwise 2 when the exact chain met a code with no table entry
+ *   inside the segment's real bits, 1 when the real bits ran out before the segment's blocks were complete, 3 as above
+ *   (and for a segment of more than 2^28 - 2^19 bytes: bit positions are 32-bit).
+ * cdn_jpeg_decode_parallel_host: the same call with HOST pointers, the same text on the calling thread. */
+size_t cdn_jpeg_parallel_workspace_bytes(int64_t max_items, int64_t max_h, int64_t max_w);
+int cdn_jpeg_decode_parallel(const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs, int64_t seg_cap,
+                             const int32_t *items, int64_t item_cap, const unsigned char *tables, unsigned char *planes,
+                             int64_t plane_stride, int32_t *status, unsigned char *out, int64_t out_cap, int rgb,
+                             unsigned char *workspace, size_t workspace_bytes, int subseq_bits, void *stream);
+int cdn_jpeg_decode_parallel_host(const unsigned char *stream_bytes, int64_t stream_cap, const int32_t *segs, int64_t seg_cap,
+                                  const int32_t *items, int64_t item_cap, const unsigned char *tables, unsigned char *planes,
+                                  int64_t plane_stride, int32_t *status, unsigned char *out, int64_t out_cap, int rgb,
+                                  unsigned char *workspace, size_t workspace_bytes, int subseq_bits);
+
 /* ------------------------------------------------------------------------------------------
  * The ctdet training criterion (main.py / quant_main.py: ModelWithLoss -> CtdetLoss, lib/trains/ctdet.py:17-74) and
  * the target maps it is fed (lib/datasets/sample/ctdet.py:87-122).  codenet_loss.hip; Python: codenet_amd/losses.py.

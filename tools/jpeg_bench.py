@@ -11,7 +11,13 @@ against the GPU path (codenet_amd.jpeg), and the two kernels alone.  GPU only; o
 restart markers: ONE segment per image, so the entropy kernel runs 64 lane-serial chains, one per image) and the same images
 encoded with a restart interval of one MCU row (24 segments per image) -- how the entropy kernel scales with the segment
 count.  The streams come from PIL when it imports (64 different images); otherwise the fixture's stream is replicated and
-the restart set is left out."""
+the restart set is left out.
+
+--entropy parallel adds the parallel entropy path (JpegDecoder(entropy="parallel", subseq_bits=--subseq_bits)) to every
+image set: (d) the launches of the serial and of the parallel decoder by HIP events, INTERLEAVED pair by pair on the same
+streams, at the batch given and at batch 1 (the first stream alone: what test.py replays per image), with the number of
+pairs in which the parallel launches were the shorter ones, and a small sweep of subseq_bits.  The two outputs must be
+torch.equal.  The yardstick is the serial path of the same run."""
 import argparse
 import io
 import json
@@ -75,7 +81,54 @@ def stats(v):
     return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3)}
 
 
-def one_set(name, datas, reps, steps, threads):
+def pair_ms(serial, parallel, out_s, out_p, pairs, warm=3):
+    """HIP-event times of serial.run and parallel.run, alternating -> (stats serial, stats parallel, pairs won)."""
+    for _ in range(warm):
+        serial.run(out_s)
+        parallel.run(out_p)
+    torch.cuda.synchronize()
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(pairs)]
+    for a, b, c, d in ev:
+        a.record()
+        serial.run(out_s)
+        b.record()
+        c.record()
+        parallel.run(out_p)
+        d.record()
+    torch.cuda.synchronize()
+    ts, tp = [a.elapsed_time(b) for a, b, _, _ in ev], [c.elapsed_time(d) for _, _, c, d in ev]
+    return stats(ts), stats(tp), sum(int(p < s) for s, p in zip(ts, tp))
+
+
+def parallel_rows(row, datas, serial, out, steps, subseq_bits, sweep):
+    """(d): the serial and the parallel launches interleaved, at the whole batch and at batch 1, and the sweep."""
+    batch = len(datas)
+    kw = dict(max_items=batch, max_h=H, max_w=W, max_stream_bytes=serial.max_stream_bytes, max_segments=serial.max_segments)
+    out_p = torch.zeros_like(out)
+    row["subseq_bits"], row["pairs"] = subseq_bits, steps
+    for S in [subseq_bits] + [s for s in sweep if s != subseq_bits]:
+        par = jpeg.JpegDecoder(entropy="parallel", subseq_bits=S, **kw)
+        for label, sub in (("batch_%d" % batch, datas), ("batch_1", datas[:1])):
+            serial.load(sub)
+            par.load(sub)
+            out.zero_()
+            out_p.zero_()
+            serial.run(out)
+            par.run(out_p)
+            serial.check()
+            par.check()
+            assert torch.equal(out, out_p), "parallel and serial outputs differ (%s, subseq_bits %d)" % (label, S)
+            ts, tp, won = pair_ms(serial, par, out, out_p, steps)
+            if S == subseq_bits:
+                row["kernels_serial_ms_" + label], row["kernels_parallel_ms_" + label] = ts, tp
+                row["parallel_below_serial_pairs_" + label] = won
+            else:
+                row.setdefault("sweep_parallel_ms_" + label, {})[str(S)] = tp
+        del par
+    serial.load(datas)
+
+
+def one_set(name, datas, reps, steps, threads, entropy="serial", subseq_bits=1024, sweep=()):
     batch = len(datas)
     infos = [jpeg.parse(d) for d in datas]
     dec = jpeg.JpegDecoder(max_items=batch, max_h=H, max_w=W, max_stream_bytes=sum(len(d) for d in datas) + 64,
@@ -122,6 +175,8 @@ def one_set(name, datas, reps, steps, threads):
     row["kernels_ms"] = event_ms(lambda: dec.run(out), steps)
     row["copy_ms"] = event_ms(lambda: static.copy_(out), steps)
     row["images_per_s_gpu_path"] = round(batch / row["gpu_ms"]["median"] * 1e3, 1)
+    if entropy == "parallel":
+        parallel_rows(row, datas, dec, out, steps, subseq_bits, sweep)
     if t_host:
         row["images_per_s_host_path"] = round(batch / row["host_ms"]["median"] * 1e3, 1)
     return row
@@ -133,6 +188,11 @@ def main():
     ap.add_argument("--reps", type=int, default=9, help="interleaved host / GPU repetitions")
     ap.add_argument("--steps", type=int, default=15, help="HIP-event pairs per kernel median")
     ap.add_argument("--threads", type=int, default=16, help="threads of the host decode")
+    ap.add_argument("--entropy", choices=("serial", "parallel"), default="serial",
+                    help="parallel: also time the parallel entropy path against the serial one, interleaved")
+    ap.add_argument("--subseq_bits", type=int, default=1024, help="sub-sequence size of the parallel path")
+    ap.add_argument("--sweep", type=int, nargs="*", default=[256, 512, 1024, 2048, 4096],
+                    help="further sub-sequence sizes timed with --entropy parallel")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "jpeg_bench needs the GPU"
     if Image is not None:
@@ -142,7 +202,8 @@ def main():
         fixture = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "jpeg_cases.npz")
         sets = [("fixture stream replicated, no restart markers", [bytes(np.load(fixture)["big_jpg"])] * args.batch)]
     for name, datas in sets:
-        print(json.dumps(one_set(name, datas, args.reps, args.steps, args.threads)), flush=True)
+        print(json.dumps(one_set(name, datas, args.reps, args.steps, args.threads, args.entropy, args.subseq_bits,
+                                 args.sweep)), flush=True)
 
 
 if __name__ == "__main__":

@@ -14,7 +14,11 @@
 // seeded single-bit flips in it, and 10 000 seeded random corruptions of the whole file (bit flips, overwritten runs,
 // inserted markers, truncations; the header included).  Every buffer is a heap block of exactly the size the library is
 // told, and the output and plane buffers carry 64 guard bytes on either side inside that block which must stay intact.
-// Exit status 0: every call returned and no guard byte changed; the sanitizers abort on anything else.
+// Every stream that reaches the decoder is also decoded by the parallel entropy path (decode_host_parallel) with
+// sub-sequences of 64 and of 1024 bits, its coefficient workspace guarded in the same way: its status must be zero
+// exactly when the serial status is zero, and then its pixels must be the serial pixels.
+// Exit status 0: every call returned, no guard byte changed and the two paths agreed; the sanitizers abort on anything
+// else.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -40,7 +44,7 @@ struct Rng {
 };
 
 struct Tally {
-  long runs = 0, refused = 0, clean = 0, flagged = 0;
+  long runs = 0, refused = 0, clean = 0, flagged = 0, parallel = 0, disagreed = 0;
 };
 
 bool guards_intact(const std::vector<uint8_t> &b) {
@@ -74,7 +78,28 @@ bool run_one(const std::vector<uint8_t> &d, Tally *t, int *status_out = nullptr)
   J::decode_host(c);
   status[0] ? ++t->flagged : ++t->clean;
   if (status_out) *status_out = status[0];
-  return guards_intact(out) && guards_intact(planes);
+  bool ok = guards_intact(out) && guards_intact(planes);
+  for (int bits : {64, 1024}) {     // the parallel entropy path on the same records
+    const int64_t work_bytes = J::par_work_stride(stride);
+    std::vector<uint8_t> out2(out.size(), 0xA5), planes2(planes.size(), 0xA5);
+    uint8_t *raw = static_cast<uint8_t *>(aligned_alloc(16, (size_t)work_bytes + 2 * kGuard));       // (kGuard keeps the 16)
+    std::vector<int32_t> status2(1, 0);
+    memset(raw, 0xA5, (size_t)work_bytes + 2 * kGuard);
+    J::ParCall pc{c, raw + kGuard, work_bytes, bits};
+    pc.c.planes = planes2.data() + kGuard;
+    pc.c.out = out2.data() + kGuard;
+    pc.c.status = status2.data();
+    J::decode_host_parallel(pc);
+    ++t->parallel;
+    for (int k = 0; k < kGuard; ++k) ok = ok && raw[k] == 0xA5 && raw[kGuard + work_bytes + k] == 0xA5;
+    free(raw);
+    ok = ok && guards_intact(out2) && guards_intact(planes2);
+    if ((status2[0] != 0) != (status[0] != 0) || (status[0] == 0 && out2 != out)) {
+      ++t->disagreed;
+      ok = false;
+    }
+  }
+  return ok;
 }
 
 std::vector<uint8_t> read_file(const char *path) {
@@ -140,8 +165,9 @@ int fuzz_file(const char *path) {
     }
     ok = run_one(d, &t);
   }
-  printf("%s: %ld runs, %ld refused by parse / pack, %ld decoded with status 0, %ld with a non-zero status, guards %s\n", path,
-         t.runs, t.refused, t.clean, t.flagged, ok ? "intact" : "DAMAGED");
+  printf("%s: %ld runs, %ld refused by parse / pack, %ld decoded with status 0, %ld with a non-zero status, %ld parallel "
+         "decodes of which %ld disagreed with the serial one, guards %s\n",
+         path, t.runs, t.refused, t.clean, t.flagged, t.parallel, t.disagreed, ok ? "intact" : "DAMAGED");
   return ok ? 0 : 1;
 }
 
