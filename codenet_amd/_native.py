@@ -141,6 +141,7 @@ _SIGNATURES = {
         + [_i, _d, _i, _vp, ctypes.c_size_t, _vp, _vp]),
     "cdn_codenet_head_range_forward": (
         _i, [_vp, _vp] + [_i64] * 4 + [_vp] * 5 + [_i, _d, _i, _vp, ctypes.c_size_t, _vp]),
+    "cdn_codenet_head_tail_max_classes": (_i, []),
     "cdn_codenet_head_tail_small_forward": (
         _i, [_vp, _vp] + [_i64] * 4 + [_vp] * 7 + [_i64, _vp, _vp]),
     "cdn_codenet_head_tail_small_q8_forward": (

@@ -988,6 +988,9 @@ stem_kernel(const float *__restrict__ img, const float *__restrict__ w, const fl
 }
 
 constexpr int kHtLD = 48;      // bytes per A / B row of one 32-channel int8 k-step (32 + 16 pad): head_small_kernel
+// most output channels of the fused head tail: four class groups of 32 on the matrix cores (54 KB of LDS per workgroup;
+// a fifth group would pass the 64 KB a workgroup may hold together with the ring and the A planes)
+constexpr int kHeadTailMaxClasses = 128;
 
 // ------------------------------------------------------------------------------------------
 // maxpool: MaxPool2d(3, stride 2, padding 1) of the "S2 + MaxPool" stems (shufflenetv2_dcn.py:209-214;
@@ -1043,11 +1046,16 @@ maxpool_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, flo
 // the 16 lanes of a pixel with a 15-shuffle transpose-reduce.  Workgroup = (image, strip of 32 stored
 // columns, strip of stored rows), ring of 4 stored rows in LDS (fake-quantised once), two rows in flight.
 // C == 64: lane = (pixel x_l = tid / 16, channel quad cq = tid % 16).
+//   MODE 2  MODE 1's result for up to kHeadTailMaxClasses classes on the int8 matrix cores, in G = ceil(classes / 32)
+//           class groups (Pascal VOC's 20 classes: G = 1; COCO's 80: G = 3): the codes of a stored row's 2 x 32 output
+//           pixels are parked as nibble planes A0 | A1, the weight codes of all groups as B0 | B1 (rows of kHtLD bytes,
+//           rows cls >= classes zero), and the 2 G tiles (output row, class group) are spread over the four waves.
+//           G is a template parameter so that G = 1 stays the code it was before there were groups.
 // Y8 (frozen serving mode): y1 holds the BYTE CODES of its QuantAct ([N][Hs*Ws][64] int8, written by the int8 pointwise
 // kernel on codes) instead of fp32 pre-quantisation values: a lane loads one 4-byte code quad and the ring receives
 // (q + zp) / scale -- the value fake_quant_r gives the fp32 element that produced the code, bit for bit.
 // ------------------------------------------------------------------------------------------
-template <int MODE, int NCLS, bool Y8 = false>
+template <int MODE, int NCLS, bool Y8 = false, int G = 1>
 __global__ void __launch_bounds__(256)
 head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1, const float *__restrict__ wdw,
                   const float *__restrict__ bdw, const unsigned *__restrict__ q2,
@@ -1055,7 +1063,7 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
                   const int *__restrict__ wsum, const float *__restrict__ bias, float *__restrict__ out,
                   cdn::QUpdate qu, int Hs, int Ws, int classes, int Cpad, int nxs, int XS,
                   int nstrips, int rps, int only_if_wide, unsigned *oflow = nullptr) {
-  // MODE 2 (up to 32 classes on the int8 matrix cores) handles codes that fit the nibble split; a batch with
+  // MODE 2 (G groups of 32 classes on the int8 matrix cores) handles codes that fit the nibble split; a batch with
   // wider codes (state[6], the first calls of a fresh running range) is left to the MODE 1 launch behind it
   // (Y8, the serving schedule: frozen ranges have no wide batches -- state[6] is 0 by construction -- and the test would
   // be a memory round trip in front of everything else in a launch that is one resident set of workgroups)
@@ -1114,26 +1122,42 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
   unsigned char *A0 = reinterpret_cast<unsigned char *>(ring4 + 4 * Wc * LPP);
   unsigned char *A1 = A0 + (size_t)2 * nrows * kHtLD;
   unsigned char *B0 = A1 + (size_t)2 * nrows * kHtLD;
-  unsigned char *B1 = B0 + (size_t)2 * 32 * kHtLD;
+  unsigned char *B1 = B0 + (size_t)G * 2 * 32 * kHtLD;          // per plane: G class groups of [k-step][32 classes]
   const int ioff = (int)z2 + (2048 - 128) - 0x4B400000;
-  float e_rinv = 0.f, e_bias = 0.f;                             // MODE 2 epilogue: this lane's class
-  int e_t128 = 0;
+  // MODE 2 matrix phase: a stored row has 2 G tiles (output row py, class group g) of 32 pixels x 32 classes; wave w
+  // owns py = w & 1 and the groups (w >> 1) + 2 j, j < NJ -- all four waves from G = 2 on, and one read of the A
+  // fragments serves every group of a wave (G = 1: waves 0 and 1 with group 0, as before there were groups)
+  constexpr int NJ = (G + 1) / 2;
+  const int mpy = G == 1 ? wave : (wave & 1);
+  auto wave_group = [&](int j) { return G == 1 ? 0 : (wave >> 1) + 2 * j; };
+  auto wave_has = [&](int j) { return G == 1 ? wave < 2 : ((G & 1) == 0 || j < NJ - 1 || wave < 2); };
+  float e_rinv[NJ], e_bias[NJ];                                 // MODE 2 epilogue: this lane's class of group j
+  int e_t128[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    e_rinv[j] = 0.f;
+    e_bias[j] = 0.f;
+    e_t128[j] = 0;
+  }
   if (MODE == 2) {
-    for (int q = tid; q < 2 * 32 * 2; q += 256) {               // k-step x class row x 16-byte piece
-      const int ks = q >> 6, cls = (q >> 1) & 31, part = (q & 1) * 16;
+    for (int q = tid; q < G * 2 * 32 * 2; q += 256) {           // group x k-step x class row x 16-byte piece
+      const int g = q >> 7, ks = (q >> 6) & 1, row = (q >> 1) & 31, cls = 32 * g + row, part = (q & 1) * 16;
       i32x4 bq = (i32x4){0, 0, 0, 0};
       if (cls < classes) bq = *reinterpret_cast<const i32x4 *>(Wq + (long)cls * Cpad + ks * 32 + part);
       i32x4 s16;
 #pragma unroll
       for (int e = 0; e < 4; ++e) s16[e] = (int)(((unsigned)bq[e] << 4) & 0xF0F0F0F0u);
-      *reinterpret_cast<i32x4 *>(B0 + (ks * 32 + cls) * kHtLD + part) = bq;
-      *reinterpret_cast<i32x4 *>(B1 + (ks * 32 + cls) * kHtLD + part) = s16;
+      *reinterpret_cast<i32x4 *>(B0 + ((g * 2 + ks) * 32 + row) * kHtLD + part) = bq;
+      *reinterpret_cast<i32x4 *>(B1 + ((g * 2 + ks) * 32 + row) * kHtLD + part) = s16;
     }
-    const int cls = lane & 31;
-    if (cls < classes) {
-      e_rinv = __fdiv_rn(1.0f, __fmul_rn(s2, wscale[cls]));
-      e_bias = bias ? bias[cls] : 0.0f;
-      e_t128 = 128 * wsum[cls];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int cls = 32 * wave_group(j) + (lane & 31);
+      if ((G == 1 || wave_has(j)) && cls < classes) {
+        e_rinv[j] = __fdiv_rn(1.0f, __fmul_rn(s2, wscale[cls]));
+        e_bias[j] = bias ? bias[cls] : 0.0f;
+        e_t128[j] = 128 * wsum[cls];
+      }
     }
   }
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1335,31 +1359,42 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
         }
         if (MODE == 2) {
           __syncthreads();                                    // the codes of this stored row are parked
-          if (wave < 2) {                                     // row block = output row py = wave
+          if (G > 1 || wave < 2) {                            // row block = output row mpy, class groups wave_group(j)
             const int fo = (lane & 31) * kHtLD + (lane >> 5) * 16;
-            i32x16 acc = (i32x16){0};
+            i32x16 acc[NJ];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[j] = (i32x16){0};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-              const i32x4 a0 = *reinterpret_cast<const i32x4 *>(A0 + (ks * nrows + wave * 2 * XS) * kHtLD + fo);
-              const i32x4 a1 = *reinterpret_cast<const i32x4 *>(A1 + (ks * nrows + wave * 2 * XS) * kHtLD + fo);
-              const i32x4 b0 = *reinterpret_cast<const i32x4 *>(B0 + (ks * 32) * kHtLD + fo);
-              const i32x4 b1 = *reinterpret_cast<const i32x4 *>(B1 + (ks * 32) * kHtLD + fo);
-              acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc, 0, 0, 0);
-            }
-            const int cls = lane & 31;
-            if (cls < classes) {
-              float *orow = out + (((long)n * classes + cls) * Ho + 2 * Y + wave) * Wo + 2 * x0;
+              const i32x4 a0 = *reinterpret_cast<const i32x4 *>(A0 + (ks * nrows + mpy * 2 * XS) * kHtLD + fo);
+              const i32x4 a1 = *reinterpret_cast<const i32x4 *>(A1 + (ks * nrows + mpy * 2 * XS) * kHtLD + fo);
 #pragma unroll
-              for (int g = 0; g < 4; ++g) {
-                const int px0 = 8 * g + 4 * (lane >> 5);
-                if (px0 < 2 * nx) {
-                  float4 o;
-                  o.x = fmaf((float)(acc[4 * g + 0] + e_t128), e_rinv, e_bias);
-                  o.y = fmaf((float)(acc[4 * g + 1] + e_t128), e_rinv, e_bias);
-                  o.z = fmaf((float)(acc[4 * g + 2] + e_t128), e_rinv, e_bias);
-                  o.w = fmaf((float)(acc[4 * g + 3] + e_t128), e_rinv, e_bias);
-                  *reinterpret_cast<float4 *>(orow + px0) = o;
+              for (int j = 0; j < NJ; ++j) {
+                if (wave_has(j)) {                            // (wave-uniform; false only for the odd group of G = 3)
+                  const int bo = ((wave_group(j) * 2 + ks) * 32) * kHtLD + fo;
+                  const i32x4 b0 = *reinterpret_cast<const i32x4 *>(B0 + bo);
+                  const i32x4 b1 = *reinterpret_cast<const i32x4 *>(B1 + bo);
+                  acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[j], 0, 0, 0);
+                  acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[j], 0, 0, 0);
+                }
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+              const int cls = 32 * wave_group(j) + (lane & 31);
+              if (wave_has(j) && cls < classes) {
+                float *orow = out + (((long)n * classes + cls) * Ho + 2 * Y + mpy) * Wo + 2 * x0;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                  const int px0 = 8 * g + 4 * (lane >> 5);
+                  if (px0 < 2 * nx) {
+                    float4 o;
+                    o.x = fmaf((float)(acc[j][4 * g + 0] + e_t128[j]), e_rinv[j], e_bias[j]);
+                    o.y = fmaf((float)(acc[j][4 * g + 1] + e_t128[j]), e_rinv[j], e_bias[j]);
+                    o.z = fmaf((float)(acc[j][4 * g + 2] + e_t128[j]), e_rinv[j], e_bias[j]);
+                    o.w = fmaf((float)(acc[j][4 * g + 3] + e_t128[j]), e_rinv[j], e_bias[j]);
+                    *reinterpret_cast<float4 *>(orow + px0) = o;
+                  }
                 }
               }
             }
@@ -1630,12 +1665,12 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
 #ifndef CDN_HS_WGS_TAIL
 #define CDN_HS_WGS_TAIL 3       /* 144-152 VGPRs: three (three heads, one box: 0.359-0.369 ms at 2 / 2, 0.352-0.355 at 4 / 3) */
 #endif
-  const int hs_wgs = mode == 0 ? CDN_HS_WGS_RANGE : CDN_HS_WGS_TAIL;      // row strips: workgroups per CU
+  const int hs_wgs_mode = mode == 0 ? CDN_HS_WGS_RANGE : CDN_HS_WGS_TAIL;      // row strips: workgroups per CU
   constexpr int hs_minrows = 8;
   hipStream_t st = cdn::as_stream(stream);
   const unsigned *q1 = static_cast<const unsigned *>(y1_qstate);
-  // geometry for strips of XS stored columns
-  auto geom = [&](int XS, int *nxs, int *nstrips, int *rps, size_t *lds, dim3 *grid) {
+  // geometry for strips of XS stored columns, hs_wgs resident workgroups per CU
+  auto geom = [&](int XS, int hs_wgs, int *nxs, int *nstrips, int *rps, size_t *lds, dim3 *grid) {
     *nxs = (int)cdn::ceil_div(Ws, XS);
     long want = cdn::ceil_div((long)hs_wgs * cdn::kCUs, (long)N * *nxs);
     *nstrips = (int)std::max<long>(1, std::min<long>(want, std::max<long>(1, Hs / hs_minrows)));
@@ -1649,7 +1684,7 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
   size_t lds;
   dim3 grid;
   const int XS = (int)std::min<int64_t>(32, Ws);
-  CDN_REQUIRE(geom(XS, &nxs, &nstrips, &rps, &lds, &grid), CDN_ERR_UNSUPPORTED, "too many workgroups");
+  CDN_REQUIRE(geom(XS, hs_wgs_mode, &nxs, &nstrips, &rps, &lds, &grid), CDN_ERR_UNSUPPORTED, "too many workgroups");
   cdn::ProfScope ps(cdn::kProfDw, (int)Hs, st);
   if (mode == 0) {
     CDN_REQUIRE(r_min && r_max && r_state, CDN_ERR_ARG, "the range pass needs x_min, x_max and state");
@@ -1662,7 +1697,8 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
     return cdn::check_launch("codenet head range");
   }
   CDN_REQUIRE(y2_qstate && w_codes && w_scale && out_nchw, CDN_ERR_ARG, "null pointer");
-  CDN_REQUIRE(classes >= 1 && classes <= 32, CDN_ERR_UNSUPPORTED, "head tail handles 1..32 output channels");
+  CDN_REQUIRE(classes >= 1 && classes <= kHeadTailMaxClasses, CDN_ERR_UNSUPPORTED,
+              "head tail handles 1..%d output channels (got %lld)", kHeadTailMaxClasses, (long long)classes);
   CDN_REQUIRE((reinterpret_cast<uintptr_t>(w_codes) & 15) == 0, CDN_ERR_ARG, "w_codes must be 16-byte aligned");
   const int Cpad = (int)((C + 63) / 64 * 64);
   const cdn::QUpdate none = cdn::no_qupdate();
@@ -1691,16 +1727,36 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
     // split (state[6]) is computed by the VALU kernel launched behind it (4 classes at a time)
     CDN_REQUIRE(mfma_ok, CDN_ERR_UNSUPPORTED,
                 "more than 4 classes need w_colsum, Ws %% 16 == 0 and a 16-byte aligned output");
-    {
+    auto matrix = [&](auto gc) -> int {
+      constexpr int G = decltype(gc)::value;                  // class groups of 32
+      // ring (18 KB) + A planes (12 KB) + 6 KB of B planes per class group: 36 / 42 / 48 / 54 KB.  The grid is sized
+      // for the workgroups a CU really holds -- by the registers three up to two groups (144-156 VGPRs) and two from
+      // three groups on (172-192: a second accumulator tile per wave), by the 160 KB of LDS 4 / 3 / 3 / 2
+      constexpr int by_regs = G <= 2 ? CDN_HS_WGS_TAIL : 2;
+      const size_t planes = (size_t)2 * 2 * (4 * 16) * kHtLD + (size_t)G * 2 * 2 * 32 * kHtLD;
+      const size_t ring = (size_t)4 * (16 + 2) * 16 * 16;
+      const int fit = (int)std::min<size_t>(by_regs, ((size_t)160 * 1024) / (ring + planes + 512));
       int nxs2, nstrips2, rps2;
       size_t lds2;
       dim3 grid2;
-      CDN_REQUIRE(geom(16, &nxs2, &nstrips2, &rps2, &lds2, &grid2), CDN_ERR_UNSUPPORTED, "too many workgroups");
-      lds2 += (size_t)2 * 2 * (4 * 16) * kHtLD + (size_t)2 * 2 * 32 * kHtLD;
-      head_small_kernel<2, 2, Y8><<<grid2, 256, lds2, st>>>(y1, q1, w_dw, b_dw, q2, w_codes, w_scale, w_colsum, bias,
-                                                            out_nchw, none, (int)Hs, (int)Ws, (int)classes,
-                                                            Cpad, nxs2, 16, nstrips2, rps2, 0, overflow);
+      CDN_REQUIRE(geom(16, fit, &nxs2, &nstrips2, &rps2, &lds2, &grid2), CDN_ERR_UNSUPPORTED, "too many workgroups");
+      lds2 += planes;
+      auto kern = head_small_kernel<2, 2, Y8, G>;
+      if (G > 1)
+        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+      kern<<<grid2, 256, lds2, st>>>(y1, q1, w_dw, b_dw, q2, w_codes, w_scale, w_colsum, bias, out_nchw, none, (int)Hs,
+                                     (int)Ws, (int)classes, Cpad, nxs2, 16, nstrips2, rps2, 0, overflow);
+      return CDN_OK;
+    };
+    static_assert(kHeadTailMaxClasses == 4 * 32, "one instantiation per number of class groups");
+    int rc_m;
+    switch ((int)((classes + 31) / 32)) {
+      case 1: rc_m = matrix(std::integral_constant<int, 1>{}); break;
+      case 2: rc_m = matrix(std::integral_constant<int, 2>{}); break;
+      case 3: rc_m = matrix(std::integral_constant<int, 3>{}); break;
+      default: rc_m = matrix(std::integral_constant<int, 4>{}); break;
     }
+    if (rc_m != CDN_OK) return rc_m;
     // the wide-code fallback behind it -- never on byte-code input: frozen ranges have no wide batches (state[6] is 0 by
     // construction, a saturating code raises the overflow flag instead), and the early-exit launch still cost 14 us per
     // head in the serving network's kernel trace
@@ -1721,6 +1777,8 @@ extern "C" int cdn_codenet_head_range_forward(const float *y1, const void *y1_qs
                            0, nullptr, r_min, r_max, r_state, bits, momentum, running, workspace, workspace_bytes,
                            stream);
 }
+
+extern "C" int cdn_codenet_head_tail_max_classes(void) { return kHeadTailMaxClasses; }
 
 extern "C" int cdn_codenet_head_tail_small_forward(const float *y1, const void *y1_qstate, int64_t N, int64_t C,
                                                    int64_t Hs, int64_t Ws, const float *w_dw, const float *b_dw,

@@ -7,6 +7,7 @@ reference's helpers with the same names and argument meaning:
     post_process / merge_outputs     lib/detectors/ctdet.py:48-72
     soft_nms                         lib/models/external/nms.pyx:77-170 (multi-scale test / --nms)
     convert_eval_format / save_results   lib/datasets/dataset/pascal.py:58-79   (results.json for tools/reval.py)
+    convert_eval_format_coco / save_results_coco   lib/datasets/dataset/coco.py:87-119 (results.json for COCOeval)
     export_w4                        packed 4-bit weight codes + per-channel scales + QuantAct ranges of a
                                      quantised model (what an integer-only deployment of the W4A8 model loads)
 """
@@ -164,6 +165,40 @@ def save_results(results, images, num_classes, save_dir):
     path = os.path.join(save_dir, "results.json")
     with open(path, "w") as f:
         json.dump(convert_eval_format(results, images, num_classes), f)
+    return path
+
+
+def _to_float(x):
+    return float("{:.2f}".format(x))
+
+
+def convert_eval_format_coco(all_bboxes, valid_ids):
+    """coco.py:87-112: all_bboxes[image_id][class (1-based)] = rows of [x1, y1, x2, y2, score] (merge_outputs' arrays, or
+    lists) -> the flat detection list COCO's evaluation loads,
+        {"image_id", "category_id": valid_ids[class - 1], "bbox": [x, y, w, h], "score"},
+    every number cut to two decimals through its decimal text.  valid_ids: the dataset's table of the 80 category ids
+    (COCO._valid_ids; the caller has the dataset object, this library carries no copy).  Width and height are formed in
+    the rows' own number type, as the reference forms them (float32 for merge_outputs' arrays).  The reference subtracts
+    in place and leaves [x1, y1, w, h, score] behind in the caller's rows; this function does NOT touch its input, so
+    converting the same results twice gives the same list."""
+    detections = []
+    for image_id in all_bboxes:
+        for cls_ind in all_bboxes[image_id]:
+            category_id = int(valid_ids[cls_ind - 1])
+            for bbox in all_bboxes[image_id][cls_ind]:
+                b = np.array(bbox)                       # (a copy in the row's own dtype)
+                b[2] -= b[0]
+                b[3] -= b[1]
+                detections.append({"image_id": int(image_id), "category_id": category_id,
+                                   "bbox": [_to_float(v) for v in b[0:4]], "score": _to_float(b[4])})
+    return detections
+
+
+def save_results_coco(results, valid_ids, save_dir):
+    """coco.py:117-119: results.json in COCO's detection layout (pycocotools' loadRes reads it)."""
+    path = os.path.join(save_dir, "results.json")
+    with open(path, "w") as f:
+        json.dump(convert_eval_format_coco(results, valid_ids), f)
     return path
 
 

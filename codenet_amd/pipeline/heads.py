@@ -241,7 +241,8 @@ class FusedHeads:
                 small = (self.small_tail and len(layers) == 3 and layers[0]["act"] is not None
                          and layers[1]["act"] is not None and layers[1]["ep"] is None and layers[1]["relu"]
                          and layers[2]["i8"] is not None and C == 64
-                         and (layers[2]["w"].shape[0] <= 4 or (layers[2]["w"].shape[0] <= 32 and Ws % 16 == 0))
+                         and (layers[2]["w"].shape[0] <= 4
+                              or (layers[2]["w"].shape[0] <= lib.cdn_codenet_head_tail_max_classes() and Ws % 16 == 0))
                          and layers[2]["act"] is None and not layers[2]["relu"])
                 if not small and name not in B["o"]:
                     B["o"][name] = torch.empty(4 * M, self._out_channels(mod), device=r.device)
@@ -266,7 +267,7 @@ class FusedHeads:
                 ep = l2["ep"] or (None, None)
                 if small:
                     # W4A8 heads: streaming range pass, then depthwise -> quantise -> 1x1 conv (<= 4 outputs: exact
-                    # integer dot products on the VALU; up to 32: int8 matrix cores) -> NCHW; the 64-channel
+                    # integer dot products on the VALU; up to the cap of 128: int8 matrix cores) -> NCHW; the 64-channel
                     # full-resolution tensor is never stored (bit-identical to the unfused schedule)
                     rec = ops._tic("head_range", (C, 2 * Hs, 2 * Ws))
                     rc = lib.cdn_codenet_head_range_forward(
@@ -306,11 +307,14 @@ class FusedHeads:
 
     # ---- frozen serving mode: the heads on the stages' byte codes --------------------------------------------
     def codes_supported(self, shape):
-        """True when every head is a W4A8 QuantDepthwiseNode (64 channels, <= 32 outputs) with both QuantActs frozen:
-        the form ``forward_codes`` implements."""
+        """True when every head is a W4A8 QuantDepthwiseNode (64 channels, outputs up to the fused tail's cap
+        cdn_codenet_head_tail_max_classes(): COCO's 80 classes included) with both QuantActs frozen: the form
+        ``forward_codes`` implements."""
+        from .. import _native as N_
         from ..portable_quantizer.quant_modules import QuantDepthwiseNode
         if shape["Co"] != 64 or not self.small_tail:
             return False
+        cap = N_.lib().cdn_codenet_head_tail_max_classes()
         for mod in self.heads.values():
             if not isinstance(mod, QuantDepthwiseNode):
                 return False
@@ -318,7 +322,7 @@ class FusedHeads:
             if not (act_fusable(a1) and act_fusable(a3)) or a1.running_stat or a3.running_stat:
                 return False
             nc = mod.quant_conv.out_channels
-            if not (nc <= 4 or (nc <= 32 and shape["W"] % 16 == 0)) or mod.quant_conv.int8_form() is None:
+            if not (nc <= 4 or (nc <= cap and shape["W"] % 16 == 0)) or mod.quant_conv.int8_form() is None:
                 return False
         return True
 

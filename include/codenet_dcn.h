@@ -815,7 +815,9 @@ int cdn_codenet_dw3x3_nhwc_forward(
  *   cdn_codenet_head_range_forward       tracks the QuantAct after the depthwise conv (r_min / r_max / r_state)
  *                                        from ReLU(dw3x3(up2(fq(y1))) + b_dw) without storing it;
  *   cdn_codenet_head_tail_small_forward  recomputes those values, quantises them with y2_qstate and applies the
- *                                        1x1 conv on the int8 matrix cores (up to 32 classes; needs w_colsum,
+ *                                        1x1 conv on the int8 matrix cores (class groups of 32, up to
+ *                                        cdn_codenet_head_tail_max_classes() classes -- 128, which covers COCO's 80;
+ *                                        more: CDN_ERR_UNSUPPORTED before any launch; needs w_colsum,
  *                                        Ws % 16 == 0 and a 16-byte aligned output), with a VALU launch behind it
  *                                        for batches whose codes are too wide for int8; other shapes with
  *                                        classes <= 4 run on the VALU form (exact integer dot products).
@@ -827,6 +829,7 @@ int cdn_codenet_head_range_forward(const float *y1, const void *y1_qstate, int64
                                    int64_t Ws, const float *w_dw, const float *b_dw, float *r_min, float *r_max,
                                    void *r_state, int bits, double momentum, int running, void *workspace,
                                    size_t workspace_bytes, void *stream);
+int cdn_codenet_head_tail_max_classes(void);
 int cdn_codenet_head_tail_small_forward(const float *y1, const void *y1_qstate, int64_t N, int64_t C, int64_t Hs,
                                         int64_t Ws, const float *w_dw, const float *b_dw, const void *y2_qstate,
                                         const signed char *w_codes, const float *w_scale, const int *w_colsum,

@@ -1,14 +1,43 @@
 """Per-kernel timing of the fused detection heads at the BASELINE shape:
-CoDeNet1x 512x512, batch 64 -> heads at 128x128 on the hot path's half-resolution output.  GPU only."""
+CoDeNet1x 512x512, batch 64 -> heads at 128x128 on the hot path's half-resolution output.  GPU only.
+    python tools/heads_bench.py [--classes 80] [--ab 10]      (--ab: the hm head's fused tail against the unfused schedule)"""
 import argparse
 import json
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from codenet_amd import harness, ops, pipeline
+
+
+def tail_ab(a, model, path, feat):
+    """The hm head on the fused tail against the unfused schedule: a.ab interleaved pairs of a.steps calls each."""
+    legs = {"fused_tail": pipeline.FusedHeads({"hm": model.hm}, small_tail=True),
+            "unfused": pipeline.FusedHeads({"hm": model.hm}, small_tail=False)}
+    r, rq, shape = path.forward_nhwc(feat)
+    for _ in range(5):                       # (running ranges: the first calls of a fresh range take the wide-code launches)
+        for h in legs.values():
+            h(r, rq, shape)
+    torch.cuda.synchronize()
+    assert "hm" not in legs["fused_tail"]._bufs["y2"] or a.fp32, "the gate sent this head to the unfused schedule"
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = {k: [] for k in legs}
+    for _ in range(a.ab):
+        for k, h in legs.items():
+            e0.record()
+            for _ in range(a.steps):
+                h(r, rq, shape)
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.steps)
+    out = {"classes": a.classes, "batch": a.batch, "res": a.res, "pairs": a.ab,
+           "pairs_won_by_fused_tail": sum(f < u for f, u in zip(ms["fused_tail"], ms["unfused"]))}
+    for k, v in ms.items():
+        out[k + "_ms"] = {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+    print(json.dumps(out))
 
 
 def main():
@@ -19,11 +48,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--one-stream", action="store_true", help="A/B: the three heads back to back on one stream")
     ap.add_argument("--graph", action="store_true", help="time a captured graph of the heads (as inside the e2e graph)")
+    ap.add_argument("--classes", type=int, default=20, help="outputs of the hm head (Pascal VOC 20, COCO 80)")
+    ap.add_argument("--ab", type=int, default=0, metavar="PAIRS",
+                    help="A/B of the hm head alone: FusedHeads(small_tail=True), the fused tail, against small_tail=False, "
+                         "the unfused schedule (depthwise store -> int8 pointwise -> unpack), PAIRS interleaved pairs")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    model = harness.create_model(quantize=not a.fp32).to(dev)
+    model = harness.create_model(heads={"hm": a.classes, "wh": 2, "reg": 2}, quantize=not a.fp32).to(dev)
     feat = pipeline.make_input(a.batch, a.res, device=dev)
     path = pipeline.FusedHotPath(model.deconv_layers)
+    if a.ab:
+        return tail_ab(a, model, path, feat)
     heads = pipeline.FusedHeads({h: getattr(model, h) for h in model.heads}, streams=not a.one_stream)
     for _ in range(5):
         heads(*path.forward_nhwc(feat))
