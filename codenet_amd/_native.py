@@ -63,6 +63,7 @@ _SIGNATURES = {
     "cdn_codenet_stage_fused_intermediates": (_i, [_i64] * 4 + [_i, _i, _i, _vp, _vp]),
     "cdn_codenet_wcodes_kb_columns": (_i64, [_i64, _i64]),
     "cdn_codenet_pwi8s_resident_workgroups": (_i, [_i64]),
+    "cdn_codenet_pointwise_i8_tile": (_i, [_i64] * 3),
     "cdn_codenet_pointwise_i8_supported": (_i, [_i64] * 4),
     "cdn_quantact_arrive_words": (_i, []),
     "cdn_codenet_scale_forward_update": (_i, [_vp] * 4 + [_i64] * 4 + [_f, _f] + [_vp] * 4 + [_i, _d, _vp, _vp]),
@@ -146,6 +147,10 @@ _SIGNATURES = {
         _i, [_vp, _vp] + [_i64] * 4 + [_vp] * 7 + [_i64, _vp, _vp]),
     "cdn_codenet_head_tail_small_q8_forward": (
         _i, [_vp, _vp] + [_i64] * 4 + [_vp] * 7 + [_i64, _vp, _vp, _vp]),
+    "cdn_codenet_head_tail_small_w_forward": (
+        _i, [_vp, _vp] + [_i64] * 4 + [_vp] * 7 + [_i64, _vp, _i, _vp]),
+    "cdn_codenet_head_tail_small_q8_w_forward": (
+        _i, [_vp, _vp] + [_i64] * 4 + [_vp] * 7 + [_i64, _vp, _vp, _i, _vp]),
     "cdn_codenet_interleave_forward": (
         _i, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
     "cdn_codenet_maxpool3x3s2_nhwc_forward": (_i, [_vp, _vp] + [_i64] * 4 + [_vp, _vp]),

@@ -507,7 +507,7 @@ struct PwCall {
   long M;
   int64_t C, Co;
   const float *w;               // fp32 weights [Co][C]
-  const signed char *w_codes;   // their 4-bit codes + w_scale [Co] + w_colsum [Co], or NULL
+  const signed char *w_codes;   // their integer codes (width: w_bits) + w_scale [Co] + w_colsum [Co], or NULL
   const float *w_scale;
   const int *w_colsum;
   const float *bias, *ep_scale, *ep_shift;      // bias [Co] or NULL; affine epilogue (BN), both or neither
@@ -518,7 +518,7 @@ struct PwCall {
   hipStream_t st;
   int64_t lda = 0, ldo = 0;     // row strides of A / R in floats (views into wider channels-last tensors); 0: dense
   const unsigned char *a_gen = nullptr;   // mixed-generation input: per channel, which state of a_state applies
-  const int *out_map = nullptr;           // output channel map (needs the 4-bit weight codes)
+  const int *out_map = nullptr;           // output channel map (needs the integer weight codes)
   // the rows of A hold lda = round_up(C, 64) valid floats (the pad repeats channel C - 1) and the weight codes are zero
   // beyond C: the int8 path runs its whole-tile form over K = lda; the f32 branch for wide codes keeps C
   bool a_padded = false;
@@ -527,6 +527,7 @@ struct PwCall {
   const float *next_ws = nullptr;
   float *sparts = nullptr;
   int n_gens = 0;               // how many states a_gen can name (0: unknown) -- pwd3_kernel then loads them all at once
+  int w_bits = 4;               // width of w_codes the caller vouches for: 4 (|q| <= 8) or 8 (CDN_W_CODES_8BIT)
 };
 int launch_pointwise(const PwCall &p);
 int pointwise_chain_parts(long M, int64_t C, int64_t Co);

@@ -72,7 +72,9 @@ __global__ void __launch_bounds__(256) frozen_params_kernel(FrozenList f) {
 // pwq8_kernel: R8[m][co] = code_r( act( (sum_c q[m][c] * qw[co][c] + zp_d * colsum[co]) / (sc_d * sw[co]) + b[co] ) )
 //   q   [M][C]      byte codes of the d quantiser, channels-last, as the gather wrote them; the sum in
 //                   brackets is sum_c level * qw, the integer pwi8_kernel forms as sum (level - 128) * qw + 128 * colsum
-//   qw  [Co][Cpad]  4-bit weight codes as int8, zero padded to a multiple of 64
+//   qw  [Co][Cpad]  weight codes as int8 (ANY int8 value: one product plane, no nibble split -- the W4A8 network's
+//                   codes lie in [-8, 7], the W8A8 network's in [-128, 127]; |sum| <= 128 * 128 * K), zero padded to a
+//                   multiple of 64
 // v_mfma_i32_32x32x32_i8: lane (r = l & 31, h = l >> 5) supplies the 16 k bytes [16h, 16h+16) of row r of a
 // 32-byte k step for both operands; C/D as f32 (column = l & 31, row = (r & 3) + 8 (r >> 2) + 4 (l >> 5)).
 // Workgroup tile BM x BN, K tiles of 64 bytes: LDS rows of 64 + 16 bytes (a quarter-wave's 16 ds_read_b128 cover
@@ -147,6 +149,8 @@ __device__ __forceinline__ void pwq8_epilogue(
   // frozen range far from zero (large |zp|) can leave int32 long before |zp| reaches 4e6 -- flagged, never silent
   // (the fp32 schedule takes its wide-code f32 branch for such ranges)
   if (((long)abs(qzi) + 128) * 8 * (long)Cpad >= (1L << 31)) bad = 1;
+  // (that bound is the one of |qw| <= 8.  Weight codes of any width -- W8A8: |qw| <= 128 -- are covered per column below,
+  // from the column's own sum: |zp * colsum| exactly, |sum q*qw| <= 128*128*Cpad)
   // Scale prediction of the NEXT stage folded in (frozen schedule only, nsc != NULL): that stage's conv_scale is
   // s_raw[m] = b + sum_co (qw_s[co] / sw) * ((q_r[m][co] + zp_r) / sc_r) -- a sum of integer products over a common
   // denominator, so I[m] = sum_co qw_s[co] * (q_r + zp_r) is accumulated HERE in exact int32 (per row over this wave's
@@ -165,6 +169,7 @@ __device__ __forceinline__ void pwq8_epilogue(
       bsv = kc.bsv[j];
       rinv = __fdiv_rn(1.0f, __fmul_rn(qs, kc.wsc[j]));
       t128 = qzi * kc.wsm[j];
+      if ((long)abs(qzi) * (long)abs(kc.wsm[j]) + 128L * 128L * (long)Cpad >= (1L << 31)) bad = 1;
       nq = kc.nq[j];
       oc = kc.oc[j];
     }

@@ -1857,10 +1857,12 @@ static int stage_fused_forward_impl(
   CDN_REQUIRE(x && w_scale && w_dw && w_pw && r_out && workspace, CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(N > 0 && C > 0 && Co > 0 && H > 0 && W > 0, CDN_ERR_ARG, "non-positive size");
   CDN_REQUIRE((x_nhwc & ~(1 | CDN_X_GATHER_MASK | CDN_X_ACT_PERCENTILE | CDN_X_WCODES_KB | CDN_X_DEFER_RANGE |
-                          CDN_X_PHASE_MASK)) == 0 &&
+                          CDN_X_PHASE_MASK | CDN_W_CODES_8BIT)) == 0 &&
                   ((x_nhwc & CDN_X_GATHER_MASK) >> 8) <= 2, CDN_ERR_ARG,
               "x_nhwc: 0 / 1, optionally | CDN_X_GATHER_PER_ITEM or CDN_X_GATHER_PERSISTENT, | CDN_X_ACT_PERCENTILE, "
-              "| CDN_X_WCODES_KB, | CDN_X_DEFER_RANGE, | CDN_X_PHASE_*");
+              "| CDN_X_WCODES_KB, | CDN_X_DEFER_RANGE, | CDN_X_PHASE_*, | CDN_W_CODES_8BIT");
+  const int w_bits = (x_nhwc & CDN_W_CODES_8BIT) ? 8 : 4;      // width of w_pw_codes the caller vouches for
+  CDN_REQUIRE(w_bits == 4 || w_pw_codes, CDN_ERR_ARG, "CDN_W_CODES_8BIT without w_pw_codes");
   // split call (multi-process global ranges): which steps run, and whether the producers only measure
   const int phases = (x_nhwc & CDN_X_PHASE_MASK) ? (x_nhwc & CDN_X_PHASE_MASK) : CDN_X_PHASE_MASK;
   const bool defer = (x_nhwc & CDN_X_DEFER_RANGE) != 0;
@@ -2013,6 +2015,7 @@ static int stage_fused_forward_impl(
   pw.lda = pad_d ? ldd : 0;
   pw.a_padded = pad_d;
   pw.w_kb = w_kb;
+  pw.w_bits = w_bits;
   pw.next_ws = next_w_scale;
   pw.sparts = parts_out;
   rc = cdn::launch_pointwise(pw);

@@ -1051,11 +1051,16 @@ maxpool_kernel(const float *__restrict__ a, const unsigned *__restrict__ aq, flo
 //           pixels are parked as nibble planes A0 | A1, the weight codes of all groups as B0 | B1 (rows of kHtLD bytes,
 //           rows cls >= classes zero), and the 2 G tiles (output row, class group) are spread over the four waves.
 //           G is a template parameter so that G = 1 stays the code it was before there were groups.
+// WB (MODE 2): width of the weight codes the caller vouches for.  4: |q| <= 8, the B1 plane holds 16 q in a byte.  8: any
+// int8 code (W8A8) -- 16 q does not fit a byte, so there is no B1 plane: the a1 products get an accumulator of their own
+// and the epilogue forms acc_lo + 16 acc_hi (int32, exact: K = 64, |acc_lo| <= 15 * 128 * 64, 16 |acc_hi| <= 2^25), the
+// split of pwi8_kernel at that width.  (MODE 1 reads the codes as fp32 values at any width: its fp32 sums are the integer
+// sums while sum |L q| < 2^24, which K = 64 and |q| <= 128 guarantee for |L| <= 2047.)
 // Y8 (frozen serving mode): y1 holds the BYTE CODES of its QuantAct ([N][Hs*Ws][64] int8, written by the int8 pointwise
 // kernel on codes) instead of fp32 pre-quantisation values: a lane loads one 4-byte code quad and the ring receives
 // (q + zp) / scale -- the value fake_quant_r gives the fp32 element that produced the code, bit for bit.
 // ------------------------------------------------------------------------------------------
-template <int MODE, int NCLS, bool Y8 = false, int G = 1>
+template <int MODE, int NCLS, bool Y8 = false, int G = 1, int WB = 4>
 __global__ void __launch_bounds__(256)
 head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1, const float *__restrict__ wdw,
                   const float *__restrict__ bdw, const unsigned *__restrict__ q2,
@@ -1144,11 +1149,15 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
       const int g = q >> 7, ks = (q >> 6) & 1, row = (q >> 1) & 31, cls = 32 * g + row, part = (q & 1) * 16;
       i32x4 bq = (i32x4){0, 0, 0, 0};
       if (cls < classes) bq = *reinterpret_cast<const i32x4 *>(Wq + (long)cls * Cpad + ks * 32 + part);
-      i32x4 s16;
+      if constexpr (WB == 4) {
+        i32x4 s16;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) s16[e] = (int)(((unsigned)bq[e] << 4) & 0xF0F0F0F0u);
-      *reinterpret_cast<i32x4 *>(B0 + ((g * 2 + ks) * 32 + row) * kHtLD + part) = bq;
-      *reinterpret_cast<i32x4 *>(B1 + ((g * 2 + ks) * 32 + row) * kHtLD + part) = s16;
+        for (int e = 0; e < 4; ++e) s16[e] = (int)(((unsigned)bq[e] << 4) & 0xF0F0F0F0u);
+        *reinterpret_cast<i32x4 *>(B0 + ((g * 2 + ks) * 32 + row) * kHtLD + part) = bq;
+        *reinterpret_cast<i32x4 *>(B1 + ((g * 2 + ks) * 32 + row) * kHtLD + part) = s16;
+      } else {
+        *reinterpret_cast<i32x4 *>(B0 + ((g * 2 + ks) * 32 + row) * kHtLD + part) = bq;
+      }
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -1364,6 +1373,11 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
             i32x16 acc[NJ];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[j] = (i32x16){0};
+            i32x16 acch[WB == 8 ? NJ : 1];                    // WB = 8: the sums of the a1 plane
+            if constexpr (WB == 8) {
+#pragma unroll
+              for (int j = 0; j < NJ; ++j) acch[j] = (i32x16){0};
+            }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
               const i32x4 a0 = *reinterpret_cast<const i32x4 *>(A0 + (ks * nrows + mpy * 2 * XS) * kHtLD + fo);
@@ -1373,15 +1387,21 @@ head_small_kernel(const float *__restrict__ y1, const unsigned *__restrict__ q1,
                 if (wave_has(j)) {                            // (wave-uniform; false only for the odd group of G = 3)
                   const int bo = ((wave_group(j) * 2 + ks) * 32) * kHtLD + fo;
                   const i32x4 b0 = *reinterpret_cast<const i32x4 *>(B0 + bo);
-                  const i32x4 b1 = *reinterpret_cast<const i32x4 *>(B1 + bo);
-                  acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[j], 0, 0, 0);
-                  acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[j], 0, 0, 0);
+                  if constexpr (WB == 4) {
+                    const i32x4 b1 = *reinterpret_cast<const i32x4 *>(B1 + bo);
+                    acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, acc[j], 0, 0, 0);
+                  } else {
+                    acc[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, acc[j], 0, 0, 0);
+                    acch[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, acch[j], 0, 0, 0);
+                  }
                 }
               }
             }
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
               const int cls = 32 * wave_group(j) + (lane & 31);
+              if constexpr (WB == 8) acc[j] += 16 * acch[j];
               if (wave_has(j) && cls < classes) {
                 float *orow = out + (((long)n * classes + cls) * Ho + 2 * Y + mpy) * Wo + 2 * x0;
 #pragma unroll
@@ -1654,7 +1674,8 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
                              const float *bias, int64_t classes, float *out_nchw, float *r_min, float *r_max,
                              void *r_state, int bits, double momentum, int running, void *workspace,
                              size_t workspace_bytes, void *stream, bool y8 = false,
-                             unsigned *overflow = nullptr) {
+                             unsigned *overflow = nullptr, int w_bits = 4) {
+  CDN_REQUIRE(w_bits == 4 || w_bits == 8, CDN_ERR_ARG, "w_bits must be 4 or 8 (got %d)", w_bits);
   CDN_REQUIRE(y1 && y1_qstate && w_dw, CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(N > 0 && Hs > 0 && Ws > 0 && N <= 65535, CDN_ERR_ARG, "bad size");
   CDN_REQUIRE(C == 64, CDN_ERR_UNSUPPORTED, "head_small is instantiated for 64 channels (got %lld)", (long long)C);
@@ -1732,8 +1753,11 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
       // ring (18 KB) + A planes (12 KB) + 6 KB of B planes per class group: 36 / 42 / 48 / 54 KB.  The grid is sized
       // for the workgroups a CU really holds -- by the registers three up to two groups (144-156 VGPRs) and two from
       // three groups on (172-192: a second accumulator tile per wave), by the 160 KB of LDS 4 / 3 / 3 / 2
-      constexpr int by_regs = G <= 2 ? CDN_HS_WGS_TAIL : 2;
-      const size_t planes = (size_t)2 * 2 * (4 * 16) * kHtLD + (size_t)G * 2 * 2 * 32 * kHtLD;
+      // (8-bit weight codes: a second accumulator tile per group -- 160-164 VGPRs on byte-code input, still three;
+      // 172-176 on fp32 input, two; 204-252 from three groups on, two)
+      const int by_regs = (G <= 2 && !(w_bits == 8 && !Y8)) ? CDN_HS_WGS_TAIL : 2;
+      // (8-bit codes: no B1 plane, half the bytes per class group -- B1 lies behind B0, so the kernel's pointers hold)
+      const size_t planes = (size_t)2 * 2 * (4 * 16) * kHtLD + (size_t)G * (w_bits == 8 ? 1 : 2) * 2 * 32 * kHtLD;
       const size_t ring = (size_t)4 * (16 + 2) * 16 * 16;
       const int fit = (int)std::min<size_t>(by_regs, ((size_t)160 * 1024) / (ring + planes + 512));
       int nxs2, nstrips2, rps2;
@@ -1741,7 +1765,7 @@ static int launch_head_small(int mode, const float *y1, const void *y1_qstate, i
       dim3 grid2;
       CDN_REQUIRE(geom(16, fit, &nxs2, &nstrips2, &rps2, &lds2, &grid2), CDN_ERR_UNSUPPORTED, "too many workgroups");
       lds2 += planes;
-      auto kern = head_small_kernel<2, 2, Y8, G>;
+      auto kern = w_bits == 8 ? head_small_kernel<2, 2, Y8, G, 8> : head_small_kernel<2, 2, Y8, G, 4>;
       if (G > 1)
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
       kern<<<grid2, 256, lds2, st>>>(y1, q1, w_dw, b_dw, q2, w_codes, w_scale, w_colsum, bias, out_nchw, none, (int)Hs,
@@ -1801,6 +1825,28 @@ extern "C" int cdn_codenet_head_tail_small_q8_forward(const signed char *y1_code
                            nullptr, 0, stream, true, overflow);
 }
 
+extern "C" int cdn_codenet_head_tail_small_w_forward(const float *y1, const void *y1_qstate, int64_t N, int64_t C,
+                                                     int64_t Hs, int64_t Ws, const float *w_dw, const float *b_dw,
+                                                     const void *y2_qstate, const signed char *w_codes,
+                                                     const float *w_scale, const int *w_colsum, const float *bias,
+                                                     int64_t classes, float *out_nchw, int w_bits, void *stream) {
+  return launch_head_small(1, y1, y1_qstate, N, C, Hs, Ws, w_dw, b_dw, y2_qstate, w_codes, w_scale, w_colsum, bias,
+                           classes, out_nchw, nullptr, nullptr, nullptr, 8, 0.99, 0, nullptr, 0, stream, false, nullptr,
+                           w_bits);
+}
+
+extern "C" int cdn_codenet_head_tail_small_q8_w_forward(const signed char *y1_codes, const void *y1_qstate, int64_t N,
+                                                        int64_t C, int64_t Hs, int64_t Ws, const float *w_dw,
+                                                        const float *b_dw, const void *y2_qstate,
+                                                        const signed char *w_codes, const float *w_scale,
+                                                        const int *w_colsum, const float *bias, int64_t classes,
+                                                        float *out_nchw, unsigned *overflow, int w_bits, void *stream) {
+  CDN_REQUIRE(overflow, CDN_ERR_ARG, "null pointer");
+  return launch_head_small(1, reinterpret_cast<const float *>(y1_codes), y1_qstate, N, C, Hs, Ws, w_dw, b_dw, y2_qstate,
+                           w_codes, w_scale, w_colsum, bias, classes, out_nchw, nullptr, nullptr, nullptr, 8, 0.99, 0,
+                           nullptr, 0, stream, true, overflow, w_bits);
+}
+
 // out[n][oy*Wo+ox][c] = max_{3x3, stride 2, pad 1} fq(a[n][..][c]): see maxpool_kernel.
 extern "C" int cdn_codenet_maxpool3x3s2_nhwc_forward(const float *a, const void *a_qstate, int64_t N, int64_t C,
                                                      int64_t H, int64_t W, float *out, void *stream) {
@@ -1853,12 +1899,16 @@ static int pwdw_s2_impl(
   CDN_REQUIRE(cdn_codenet_pwdw_s2_supported(N, Cin, C, H, W), CDN_ERR_UNSUPPORTED, "shape outside the fused pw -> dw kernel");
   CDN_REQUIRE(ld_x >= Cin && (ld_x & 3) == 0 && ld_out >= C && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(w_pw_codes) & 15) == 0, CDN_ERR_ARG, "bad row stride / alignment");
+  // running | CDN_W_CODES_8BIT: the width of w_pw_codes, for the range-only pass (the recomputing kernel applies the 16
+  // to the sum of the high plane and needs no flag)
+  const int wflag = running & CDN_W_CODES_8BIT;
+  running &= ~CDN_W_CODES_8BIT;
   // 1. the 1x1 conv as a RANGE-ONLY pass (out = NULL): batch extremes of relu(conv) -> the mid QuantAct
   const int64_t M = N * H * W;
   int rc = 0;
   if (range_pass)
     rc = cdn_codenet_pointwise_mixed_forward(x, x_qstate, nullptr, M, Cin, C, ld_x, 0, w_pw, w_pw_codes, w_pw_scale,
-                                             w_pw_colsum, bias_pw, nullptr, nullptr, 1, nullptr, m_min, m_max, m_state,
+                                             w_pw_colsum, bias_pw, nullptr, nullptr, 1 | wflag, nullptr, m_min, m_max, m_state,
                                              bits, momentum, running, workspace, workspace_bytes, nullptr, stream);
   if (rc) return rc;
   // 2. conv recomputed into the ring rows of the stride-2 depthwise

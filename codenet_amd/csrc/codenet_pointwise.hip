@@ -523,6 +523,12 @@ pws_kernel(const float *__restrict__ A, const float *__restrict__ Wp, const floa
 // the final fp32 scale and bias add.  Operand lane map: lane (r = l&31, h = l>>5) supplies 16
 // consecutive k bytes [16h, 16h+16) of its row's 32-byte k-step for BOTH operands (any k order works as long as A
 // and B agree; checked with exact integer data, tools/probes/probe_i8.hip); C/D map as f32.
+// WB = 8 (W8A8: qw in [-128, 127], the caller says so with CDN_W_CODES_8BIT): 16*qw no longer fits a byte, so the factor
+// 16 moves off the weight plane -- the a1 products get an accumulator of their own and the epilogue forms
+// acc_lo + 16*acc_hi in int32 in front of the unchanged expression.  Bound (state word 6 clear, C <= 4096, which the
+// launcher checks): |sum a0*qw| <= 15*128*4096 < 2^23, 16*|sum a1*qw| <= 16*128*128*4096 = 2^30, their sum is
+// sum (L-128)*qw with |L-128| <= 2040: <= 2040*128*4096 = 1 069 547 520, and |128*colsum| <= 128*128*4096 = 2^26 on top:
+// every intermediate stays below 2^31.  No B1 plane in LDS.  WB = 4 is the code it was.
 // Tried in round 3 and removed (source kept in tools/probes/archive/pwi8r_kernel.inc): the same kernel with the raw fp32 A / int8 B tiles fetched by
 // global_load_lds into a 3-slot LDS ring two tiles ahead (counted vmcnt, no compiler-visible load in the k loop,
 // bit-identical results) -- stage 0 (K = 1024) 39.7 vs 38.3 us, stage 1 (K = 256, only two 72-KB workgroups per CU
@@ -623,7 +629,7 @@ __device__ __forceinline__ void pwi8_wide_path(const float *__restrict__ A, cons
 
 // (round 6: the kernel body as a device function of (m0, n0, partial index, partial count), so that the detection heads'
 // launch -- three 64-column problems on one A operand, pwi8h_kernel below -- maps its workgroups itself)
-template <int BM, int BN, int WGM, bool FAST>
+template <int BM, int BN, int WGM, bool FAST, int WB = 4>
 __device__ __forceinline__ void
 pwi8_body(const float *__restrict__ A, const unsigned *__restrict__ aq,
           const signed char *__restrict__ Wq, const float *__restrict__ wscale,
@@ -640,7 +646,8 @@ pwi8_body(const float *__restrict__ A, const unsigned *__restrict__ aq,
   __shared__ __attribute__((aligned(16))) unsigned char A0[2][BM * kI8LD];
   __shared__ __attribute__((aligned(16))) unsigned char A1[2][BM * kI8LD];
   __shared__ __attribute__((aligned(16))) unsigned char B0[2][BN * kI8LD];
-  __shared__ __attribute__((aligned(16))) unsigned char B1[2][BN * kI8LD];
+  static_assert(WB == 4 || WB == 8, "weight code width: 4 (16*qw plane) or 8 (second accumulator)");
+  __shared__ __attribute__((aligned(16))) unsigned char B1[WB == 4 ? 2 : 1][WB == 4 ? BN * kI8LD : 16];
   CDN_STAMPR(2, 0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave / WGN) * TM * 32, wn = (wave % WGN) * TN * 32;
@@ -729,6 +736,13 @@ pwi8_body(const float *__restrict__ A, const unsigned *__restrict__ aq,
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = (i32x16){0};
+  i32x16 acch[WB == 8 ? TM : 1][WB == 8 ? TN : 1];      // WB = 8: the sums of the a1 plane
+  if constexpr (WB == 8) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acch[i][j] = (i32x16){0};
+  }
   auto ucode = [&](float v, bool live) -> unsigned {
 #pragma clang fp contract(off)
 #if defined(CDN_DIAG) && CDN_DIAG == 7   // diagnostic build: no fp32 -> code arithmetic (wrong results)
@@ -758,11 +772,13 @@ pwi8_body(const float *__restrict__ A, const unsigned *__restrict__ aq,
 #pragma unroll
     for (int i = 0; i < BI; ++i)
       if (br + 128 * i < BN) {
-        i32x4 s16;   // 16*qw per byte: shift each byte left by 4 (qw in [-8,7] -> no carry loss)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s16[e] = (int)(((unsigned)b[i][e] << 4) & 0xF0F0F0F0u);
         *reinterpret_cast<i32x4 *>(&B0[buf][(br + 128 * i) * kI8LD + bh]) = b[i];
-        *reinterpret_cast<i32x4 *>(&B1[buf][(br + 128 * i) * kI8LD + bh]) = s16;
+        if constexpr (WB == 4) {
+          i32x4 s16;   // 16*qw per byte: shift each byte left by 4 (qw in [-8,7] -> no carry loss)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s16[e] = (int)(((unsigned)b[i][e] << 4) & 0xF0F0F0F0u);
+          *reinterpret_cast<i32x4 *>(&B1[buf][(br + 128 * i) * kI8LD + bh]) = s16;
+        }
       }
   };
 
@@ -784,7 +800,7 @@ pwi8_body(const float *__restrict__ A, const unsigned *__restrict__ aq,
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       b0[j] = *reinterpret_cast<const i32x4 *>(&B0[buf][(wn + j * 32) * kI8LD + fo]);
-      b1[j] = *reinterpret_cast<const i32x4 *>(&B1[buf][(wn + j * 32) * kI8LD + fo]);
+      if constexpr (WB == 4) b1[j] = *reinterpret_cast<const i32x4 *>(&B1[buf][(wn + j * 32) * kI8LD + fo]);
     }
     // (low nibbles for every accumulator, then the high parts: two MFMAs into the same accumulator back to back
     // wait for each other; the integer sum does not depend on the order)
@@ -796,8 +812,10 @@ pwi8_body(const float *__restrict__ A, const unsigned *__restrict__ aq,
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[i], b1[j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < TN; ++j) {
+        if constexpr (WB == 4) acc[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[i], b1[j], acc[i][j], 0, 0, 0);
+        else acch[i][j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[i], b0[j], acch[i][j], 0, 0, 0);
+      }
     if (t + 1 < nk) store_tile(buf ^ 1, (t + 1) * 32);
     __syncthreads();
   }
@@ -815,7 +833,9 @@ pwi8_body(const float *__restrict__ A, const unsigned *__restrict__ aq,
       for (int r = 0; r < 16; ++r) {
         const long m = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (m < M && co < Co) {
-          float v = fmaf((float)(acc[i][j][r] + t128), rinv, bsv);
+          int sum = acc[i][j][r];
+          if constexpr (WB == 8) sum += 16 * acch[i][j][r];      // (exact: see the bound in the header)
+          float v = fmaf((float)(sum + t128), rinv, bsv);
           if (relu) v = cdn::relu_keep_nan(v);
           if (R) R[m * ldo + oc] = v;                          // (R == NULL: range-only pass)
           mn = fminf(mn, v);
@@ -844,6 +864,21 @@ pwi8_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq,
                                gridDim.x * gridDim.y);
 }
 
+// the same body on 8-bit weight codes (CDN_W_CODES_8BIT).  A kernel of its own name: the 4-bit instantiations above keep
+// their symbols, their registers and their LDS
+template <int BM, int BN, int WGM, bool FAST>
+__global__ void __launch_bounds__(256)
+pwi8w_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq,
+             const signed char *__restrict__ Wq, const float *__restrict__ wscale,
+             const int *__restrict__ wsum, const float *__restrict__ Wp,
+             const float *__restrict__ bias, float *__restrict__ R,
+             cdn::QUpdate qu, long M, int C, int Cpad, int Co, int relu, int lda,
+             int ldo, const int *__restrict__ omap, int Cw) {
+  pwi8_body<BM, BN, WGM, FAST, 8>(A, aq, Wq, wscale, wsum, Wp, bias, R, qu, M, C, Cpad, Co, relu, lda, ldo, omap, Cw,
+                                  (long)blockIdx.x * BM, blockIdx.y * BN, blockIdx.y * gridDim.x + blockIdx.x,
+                                  gridDim.x * gridDim.y);
+}
+
 // pwi8h_kernel (round 6; VERDICT r5 "next" #1a): the FIRST 1x1 convs of the detection heads -- NH problems of 64 output
 // columns each on ONE A operand (the last stage's output r, 67 MB at batch 64, which three separate launches on three
 // streams read three times) -- as one launch.  Weights / scales / column sums / biases are the heads' concatenated
@@ -854,7 +889,7 @@ pwi8_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq,
 struct QUpdateN {
   cdn::QUpdate q[4];
 };
-template <int NH>
+template <int NH, int WB = 4>
 __global__ void __launch_bounds__(256)
 pwi8h_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq, const signed char *__restrict__ Wq,
              const float *__restrict__ wscale, const int *__restrict__ wsum, const float *__restrict__ Wp,
@@ -871,8 +906,8 @@ pwi8h_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq, const
     head = q / rem;
     mt = full / NH + q % rem;
   }
-  pwi8_body<64, 64, 2, true>(A, aq, Wq, wscale, wsum, Wp, bias, R + (long)head * head_stride, qus.q[head],
-                             M, C, Cpad, 64 * NH, relu, lda, 64, omap, C, (long)mt * 64, head * 64, mt, ntm);
+  pwi8_body<64, 64, 2, true, WB>(A, aq, Wq, wscale, wsum, Wp, bias, R + (long)head * head_stride, qus.q[head],
+                                 M, C, Cpad, 64 * NH, relu, lda, 64, omap, C, (long)mt * 64, head * 64, mt, ntm);
 }
 
 
@@ -1145,11 +1180,11 @@ pwi8s_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq, const
   }
 }
 // ------------------------------------------------------------------------------------------
-// pwb3: the W4 pointwise conv on FINAL (already fake-quantised, or fp32) activations -- the first 1x1 of a
+// pwb3: the integer-weight (W4 / W8) pointwise conv on FINAL (already fake-quantised, or fp32) activations -- the first 1x1 of a
 // ShuffleNetV2 unit, whose input channels carry different generations of the layer's running QuantAct and
 // so have no common integer grid.  Exact products on the bf16 matrix cores:
 //   x = hi + mid + lo   (three bf16 terms by truncation: 8 + 8 + 8 significant bits, the split is EXACT)
-//   weights  qw in [-8, 7] are exact in bf16,  W' = qw / sw[co]
+//   weights  qw (int8: [-8, 7] in the W4A8 network, [-128, 127] at W8A8) are exact in bf16,  W' = qw / sw[co]
 //   y[m][co] = (sum_c hi*qw + sum_c mid*qw + sum_c lo*qw) / sw[co] + b
 // every product is exact in fp32 and the accumulation is fp32, as in the f32 MFMA kernel, at 3 of the
 // 16x faster v_mfma_f32_32x32x16_bf16 per 16 k instead of 8 v_mfma_f32_32x32x2f32 (measured: the f32 form
@@ -1349,7 +1384,7 @@ pwb3_kernel(const float *__restrict__ A, const unsigned *__restrict__ aq,
 }
 
 // ------------------------------------------------------------------------------------------
-// pwd3: the same arithmetic as pwb3 (exact bf16 x 3 split against 4-bit weight codes) as a STREAMING
+// pwd3: the same arithmetic as pwb3 (exact bf16 x 3 split against int8 weight codes of any width) as a STREAMING
 // kernel for the shapes of the ShuffleNetV2 units (Co <= a few hundred, C <= 512): in pwb3 no two waves
 // share a row of A (each wave owns 32 rows x the whole N tile), so staging A through LDS only re-shapes it
 // -- and costs two barriers per 32 k with the load latency exposed between them (measured 44 us for
@@ -1754,6 +1789,41 @@ extern "C" int64_t cdn_codenet_wcodes_kb_offset(int64_t C, int64_t Co) {
   return C > 0 && Co > 0 ? (Co * ((C + 63) / 64 * 64) + 255) / 256 * 256 : 0;
 }
 
+// The tile of the tiled int8 pointwise (pwi8_kernel / pwi8w_kernel) for M rows, K = Kt and Co columns, as
+// rows * 1000 + columns: launch_pointwise switches on it and cdn_codenet_pointwise_i8_tile answers it to tests.
+// Co > 64: 64-row tiles (36 KiB LDS, 112 VGPRs: four workgroups per CU; measured at stage 1
+// 26.3 us vs 30.6 us with 128-row tiles; 32-row tiles change nothing at stage 0: 40.2 vs 40.7 us)
+// round 4: when 64-row tiles leave the chip with at most ONE workgroup per CU (CoDeNet2x stage 0 at 32 images:
+// M = 8192, K = 2176 -- a chain of 68 dependent k tiles per workgroup and nothing beside it), 32-row tiles give
+// every CU two chains to interleave
+// ... and 32-row tiles for the K < 256 launches of layers 2-3 (unit exits, the stride-2 units' branch convs; round 4):
+// whole network 2.564 / 2.603 -> 2.544 / 2.533 ms on one box.  NOT for K = 256 (stage 1 of the deform path: 0.2442 ->
+// 0.2500 ms per step with them) and not at K >= 512, where nothing moved.
+// Co <= 64 (layer 1's units, the heads' first conv, stage 2): 64 x 64 tiles on the large-M launches (round 4).  Alone
+// on the GPU the 128 x 64 tiles are as fast (33.1 vs 31.6 us at 262 144 x 58 -> 58, 38.4 vs 39.9 at K = 128), inside
+// the network -- beside the other branch / the other heads -- the smaller tiles are worth 38 us per batch (whole
+// network 2.594-2.599 -> 2.552-2.561 ms, three interleaved pairs on one box; the deform step itself: unchanged)
+static int pwi8_tile(long M, int64_t Kt, int64_t Co) {
+  if (Co > 64) {
+#if !defined(CDN_NO_PWI32)
+    if (cdn::ceil_div(M, 64) * cdn::ceil_div(Co, 128) <= cdn::kCUs && Kt >= 1024) return 32128;
+#endif
+#if !defined(CDN_PWI_NO_32ROWS)
+    if (Kt < 256) return 32128;
+#endif
+    return 64128;
+  }
+#if !defined(CDN_PWI_NO_64X64)
+  if (M >= 65536) return 64064;
+#endif
+  return 128064;
+}
+// diagnostics / tests: the tile (rows * 1000 + columns) the tiled int8 pointwise takes for a dense [M][C] input; the
+// same for 4- and 8-bit codes (8-bit codes never take the streaming kernel, which this does not describe)
+extern "C" int cdn_codenet_pointwise_i8_tile(int64_t M, int64_t C, int64_t Co) {
+  return (M > 0 && C > 0 && Co > 0) ? pwi8_tile((long)M, C, Co) : 0;
+}
+
 // planes of partial sums a chained fp32 pointwise of this shape leaves (cdn_codenet_stage_chain_parts): the column tiles
 // of pws_kernel, 0 when the launch would not take that kernel
 int cdn::pointwise_chain_parts(long M, int64_t C, int64_t Co) {
@@ -1782,15 +1852,16 @@ int cdn::launch_pointwise(const cdn::PwCall &p) {
     if (pw_fast) CDN_PW1(BM_, BN_, WGM_, AQ_, true);                      \
     else CDN_PW1(BM_, BN_, WGM_, AQ_, false);                             \
   } while (0)
+  CDN_REQUIRE(p.w_bits == 4 || p.w_bits == 8, CDN_ERR_ARG, "weight code width must be 4 or 8");
   const bool use_i8 = p.w_codes != nullptr && p.a_state != nullptr && p.ep_scale == nullptr && p.a_gen == nullptr;
-  // final-valued input (no QuantAct state to derive integer codes from) with 4-bit weight codes: exact
-  // bf16 x 3 split instead of f32 MFMA
+  // final-valued input (no QuantAct state to derive integer codes from) with integer weight codes (any int8 value:
+  // |q| <= 128 is exact in bf16): exact bf16 x 3 split instead of f32 MFMA
   const bool use_b3 = p.w_codes != nullptr && p.ep_scale == nullptr && p.w_scale != nullptr &&
                       (p.a_gen != nullptr || p.a_state == nullptr);
   CDN_REQUIRE(p.a_gen == nullptr || (use_b3 && p.a_state != nullptr && C <= kMixedMaxC), CDN_ERR_UNSUPPORTED,
-              "a mixed-generation input needs the states, 4-bit weight codes and C <= %d", kMixedMaxC);
+              "a mixed-generation input needs the states, the integer weight codes and C <= %d", kMixedMaxC);
   CDN_REQUIRE(p.out_map == nullptr || use_i8 || use_b3, CDN_ERR_UNSUPPORTED,
-              "an output channel map needs the 4-bit weight codes");
+              "an output channel map needs the integer weight codes");
   const int only_if_wide = 0;
   if (use_i8) {
     CDN_REQUIRE(p.w_scale && p.w_colsum, CDN_ERR_ARG, "int8 pointwise needs scale and colsum");
@@ -1803,11 +1874,18 @@ int cdn::launch_pointwise(const cdn::PwCall &p) {
   do {                                                                                                     \
     dim3 g((unsigned)cdn::ceil_div(M, BM_), (unsigned)cdn::ceil_div(Co, BN_));                             \
     auto kern = pw_fast ? pwi8_kernel<BM_, BN_, WGM_, true> : pwi8_kernel<BM_, BN_, WGM_, false>;          \
+    if (p.w_bits == 8) kern = pw_fast ? pwi8w_kernel<BM_, BN_, WGM_, true> : pwi8w_kernel<BM_, BN_, WGM_, false>; \
     kern<<<g, 256, 0, st>>>(p.a, p.a_state, p.w_codes, p.w_scale, p.w_colsum, p.w, p.bias, p.out, p.qu, M, \
                             (int)Kt, Cpad, (int)Co, p.relu, (int)lda, (int)ldo, p.out_map, (int)C);        \
   } while (0)
-    // long-K launches with the k-blocked copy of the codes at hand (the fused stage, stage 0): the streaming kernel
-    if (pwi8s_applies(M, Kt, Cpad, Co, pw_fast, p.w_kb)) {
+    // 8-bit codes: the bound of the second accumulator (pwi8_body) is stated for K <= 4096
+    CDN_REQUIRE(p.w_bits != 8 || Kt <= 4096, CDN_ERR_UNSUPPORTED, "8-bit weight codes need C <= 4096 (got %lld)",
+                (long long)Kt);
+    // long-K launches with the k-blocked copy of the codes at hand (the fused stage, stage 0): the streaming kernel.
+    // 4-bit codes only: its two accumulator sets for 8-bit codes are 2 x 64 registers at TN = 4 -- all 128 a wave has
+    // at the four workgroups per CU the kernel is built around -- so 8-bit long-K launches take the tiled kernel below
+    // (the k-blocked copy, when given, is simply not read)
+    if (p.w_bits != 8 && pwi8s_applies(M, Kt, Cpad, Co, pw_fast, p.w_kb)) {
       const long nrb = cdn::ceil_div(M, 32);
       const int ncg = Co > 128 ? 2 : 1;
       const unsigned grid = (unsigned)(nrb * ncg);
@@ -1817,31 +1895,12 @@ int cdn::launch_pointwise(const cdn::PwCall &p) {
                                     (int)Co, p.relu, (int)lda, (int)ldo, p.out_map, (int)C, ncg);
       return cdn::check_launch("codenet int8 pointwise (streaming)");
     }
-    // Co > 64: 64-row tiles (36 KiB LDS, 112 VGPRs: four workgroups per CU; measured at stage 1
-    // 26.3 us vs 30.6 us with 128-row tiles; 32-row tiles change nothing at stage 0: 40.2 vs 40.7 us)
-    // round 4: when 64-row tiles leave the chip with at most ONE workgroup per CU (CoDeNet2x stage 0 at 32 images:
-    // M = 8192, K = 2176 -- a chain of 68 dependent k tiles per workgroup and nothing beside it), 32-row tiles give
-    // every CU two chains to interleave
-#if !defined(CDN_NO_PWI32)
-    if (pw_bn == 128 && cdn::ceil_div(M, 64) * cdn::ceil_div(Co, 128) <= cdn::kCUs && Kt >= 1024) CDN_PWI(32, 128, 1);
-    else
-#endif
-    // ... and 32-row tiles for the K < 256 launches of layers 2-3 (unit exits, the stride-2 units' branch convs; round 4):
-    // whole network 2.564 / 2.603 -> 2.544 / 2.533 ms on one box.  NOT for K = 256 (stage 1 of the deform path: 0.2442 ->
-    // 0.2500 ms per step with them) and not at K >= 512, where nothing moved.
-#if !defined(CDN_PWI_NO_32ROWS)
-    if (pw_bn == 128 && Kt < 256) CDN_PWI(32, 128, 1);
-    else
-#endif
-    if (pw_bn == 128) CDN_PWI(64, 128, 2);
-    // Co <= 64 (layer 1's units, the heads' first conv, stage 2): 64 x 64 tiles on the large-M launches (round 4).  Alone
-    // on the GPU the 128 x 64 tiles are as fast (33.1 vs 31.6 us at 262 144 x 58 -> 58, 38.4 vs 39.9 at K = 128), inside
-    // the network -- beside the other branch / the other heads -- the smaller tiles are worth 38 us per batch (whole
-    // network 2.594-2.599 -> 2.552-2.561 ms, three interleaved pairs on one box; the deform step itself: unchanged)
-#if !defined(CDN_PWI_NO_64X64)
-    else if (M >= 65536) CDN_PWI(64, 64, 2);
-#endif
-    else CDN_PWI(128, 64, 4);
+    switch (pwi8_tile(M, Kt, Co)) {      // (the reasons and the measurements: pwi8_tile)
+      case 32128: CDN_PWI(32, 128, 1); break;
+      case 64128: CDN_PWI(64, 128, 2); break;
+      case 64064: CDN_PWI(64, 64, 2); break;
+      default: CDN_PWI(128, 64, 4); break;
+    }
 #undef CDN_PWI
     // (wide codes, state[6] != 0, are handled by the f32 branch inside pwi8_kernel)
   } else if (use_b3) {
@@ -1962,6 +2021,10 @@ extern "C" int cdn_codenet_pointwise_mixed_forward_n(
     void *workspace, size_t workspace_bytes, float *out, void *stream) {
   CDN_REQUIRE(a && w, CDN_ERR_ARG, "null pointer");
   CDN_REQUIRE(n_gens >= 0, CDN_ERR_ARG, "n_gens must be >= 0 (0: unknown)");
+  // relu | CDN_W_CODES_8BIT: w_codes may hold any int8 value (W8A8); without it the int8 kernels assume |q| <= 8
+  const int w_bits = (relu & CDN_W_CODES_8BIT) ? 8 : 4;
+  relu &= ~CDN_W_CODES_8BIT;
+  CDN_REQUIRE(w_bits == 4 || w_codes, CDN_ERR_ARG, "CDN_W_CODES_8BIT without w_codes");
   // out == NULL: RANGE-ONLY pass (round 4) -- the kernel computes everything and stores nothing; only the int8 kernel
   // on one input state implements it
   CDN_REQUIRE(out || (r_state && a_qstate && !a_gen && w_codes && !ep_scale), CDN_ERR_ARG,
@@ -2001,6 +2064,7 @@ extern "C" int cdn_codenet_pointwise_mixed_forward_n(
   pw.a_gen = a_gen;
   pw.out_map = out_map;
   pw.n_gens = n_gens;
+  pw.w_bits = w_bits;
   return cdn::launch_pointwise(pw);
 }
 
@@ -2018,6 +2082,9 @@ extern "C" int cdn_codenet_heads_pointwise_forward(
   CDN_REQUIRE(a && a_qstate && w && w_codes && w_scale && w_colsum && r_min && r_max && r_state && workspaces && out_map &&
                   out,
               CDN_ERR_ARG, "null pointer");
+  const int w_bits = (relu & CDN_W_CODES_8BIT) ? 8 : 4;      // (as in cdn_codenet_pointwise_nhwc_forward)
+  relu &= ~CDN_W_CODES_8BIT;
+  CDN_REQUIRE(w_bits == 4 || C <= 4096, CDN_ERR_UNSUPPORTED, "8-bit weight codes need C <= 4096 (got %lld)", (long long)C);
   CDN_REQUIRE(cdn_codenet_heads_pointwise_supported(M, C, n_heads), CDN_ERR_UNSUPPORTED,
               "heads launch: 2-4 heads of 64 columns, C %% 32 == 0 (cdn_codenet_heads_pointwise_supported)");
   CDN_REQUIRE(bits >= 2 && bits <= 16, CDN_ERR_ARG, "bits must be in [2,16], got %d", bits);
@@ -2037,8 +2104,11 @@ extern "C" int cdn_codenet_heads_pointwise_forward(
   hipStream_t st = cdn::as_stream(stream);
   const unsigned *aq = static_cast<const unsigned *>(a_qstate);
 #define CDN_PWH(NH_)                                                                                                \
-  pwi8h_kernel<NH_><<<grid, 256, 0, st>>>(a, aq, w_codes, w_scale, w_colsum, w, bias, out, qus, (long)M, (int)C, Cpad, \
-                                          relu, (int)C, out_map, (long)head_stride)
+  do {                                                                                                              \
+    auto kern = w_bits == 8 ? pwi8h_kernel<NH_, 8> : pwi8h_kernel<NH_, 4>;                                          \
+    kern<<<grid, 256, 0, st>>>(a, aq, w_codes, w_scale, w_colsum, w, bias, out, qus, (long)M, (int)C, Cpad, relu,   \
+                               (int)C, out_map, (long)head_stride);                                                 \
+  } while (0)
   if (n_heads == 2) CDN_PWH(2);
   else if (n_heads == 3) CDN_PWH(3);
   else CDN_PWH(4);

@@ -12,7 +12,7 @@ of parameters and buffers (weights, BN statistics, QuantAct ranges) from rank 0 
 Round 6: split by concern into the modules of this package -- common (shared pieces), distributed, hotpath
 (FusedHotPath), heads (FusedHeads), backbone (FusedBackbone), serving (calibration, FrozenHotPath, FrozenBackbone),
 training (GraphedTrainStep); every name stays importable from `codenet_amd.pipeline`."""
-from .common import (BN_MOMENTUM, stage_shapes, DeconvLayers, build_hot_path, make_input, set_running_stat, GATHER_PER_ITEM, GATHER_PERSISTENT, OverflowFlags, ACT_PERCENTILE, WCODES_KB, DEFER_RANGE, PHASE_SCALE, PHASE_GATHER, PHASE_POINTWISE, stage_int8_codes, act_fusable, global_range_active, uniform_act_settings, algorithmic_bytes, bn_affine)      # noqa: F401
+from .common import (BN_MOMENTUM, stage_shapes, DeconvLayers, build_hot_path, make_input, set_running_stat, GATHER_PER_ITEM, GATHER_PERSISTENT, OverflowFlags, ACT_PERCENTILE, WCODES_KB, W_CODES_8BIT, DEFER_RANGE, PHASE_SCALE, PHASE_GATHER, PHASE_POINTWISE, stage_int8_codes, act_fusable, global_range_active, uniform_act_settings, algorithmic_bytes, bn_affine)      # noqa: F401
 from .distributed import (broadcast_parameters, exchange_shard_sizes, gather_detections, set_global_range, shard_range)      # noqa: F401
 from .hotpath import (FusedHotPath)      # noqa: F401
 from .heads import (FusedHeads)      # noqa: F401

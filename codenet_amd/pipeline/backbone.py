@@ -51,7 +51,7 @@ class FusedBackbone:
             cp = torch.zeros(Co, (K + 63) // 64 * 64, dtype=torch.int8, device=dev)
             cp[:, :K] = codes[:, cols]
             W4 = dict(w=w.reshape(Co, -1)[:, cols].contiguous(), codes=cp, scale=scale, colsum=colsum,
-                      bias=b.contiguous(), Co=Co, K=K)
+                      bias=b.contiguous(), Co=Co, K=K, wflag=q4.int8_width_flag())
             self._l4_cache = (key, W4)
         return self._l4_cache[1]
 
@@ -120,14 +120,16 @@ class FusedBackbone:
         from .. import _native as N_
         w, b = self._folded(convbn)
         Co, C = w.shape[0], w.shape[1]
-        # 4-bit codes: integer MFMA when the input carries a QuantAct state, exact bf16 split otherwise
+        # integer codes: integer MFMA when the input carries a QuantAct state, exact bf16 split otherwise; codes wider than
+        # 4 bits are announced to the library (CDN_W_CODES_8BIT in `relu`)
         i8 = convbn.folded_int8() if (self.int8 and not isinstance(convbn, tuple)) else None
+        wflag = convbn.int8_width_flag() if i8 is not None else 0
         i8 = i8 if i8 is not None else (None, None, None)
         ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         w2 = w.reshape(Co, C)
         rc = N_.lib().cdn_codenet_pointwise_nhwc_forward(
             a_ptr, a_q, M, C, Co, lda, ldo, w2.data_ptr(), ptr(i8[0]), ptr(i8[1]), ptr(i8[2]), ptr(b),
-            None, None, int(relu), *self._act_args(act, out.device), ctx.ws_ptr, ctx.ws_bytes,
+            None, None, int(relu) | wflag, *self._act_args(act, out.device), ctx.ws_ptr, ctx.ws_bytes,
             out.data_ptr(), ctx.stream)
         N_.check(rc, "cdn_codenet_pointwise_nhwc_forward")
 
@@ -324,7 +326,7 @@ class FusedBackbone:
             cp = torch.zeros(Co, kpad, dtype=torch.int8, device=dev)
             cp[:, :K] = codes[:, src] * live.to(torch.int8)
             out = dict(w=w2.contiguous(), codes=cp.contiguous(), scale=scale, colsum=colsum, bias=b.contiguous(),
-                       Co=Co, K=K)
+                       Co=Co, K=K, wflag=convbn.int8_width_flag())
             return out
 
         plan = dict(key=key, h=h, cin=cin, C=C, units=[])
@@ -407,8 +409,8 @@ class FusedBackbone:
             aa[2] = state_ptr
         rc = N_.lib().cdn_codenet_pointwise_mixed_forward_n(
             a_ptr, a_q, a_gen, n_gens if (a_gen and self.preload_states) else 0, M, Wt["K"], Wt["Co"], lda, ldo, Wt["w"].data_ptr(), Wt["codes"].data_ptr(),
-            Wt["scale"].data_ptr(), Wt["colsum"].data_ptr(), Wt["bias"].data_ptr(), None, None, int(relu),
-            out_map, *aa, ctx.ws_ptr, ctx.ws_bytes, out_ptr, ctx.stream)
+            Wt["scale"].data_ptr(), Wt["colsum"].data_ptr(), Wt["bias"].data_ptr(), None, None,
+            int(relu) | Wt.get("wflag", 0), out_map, *aa, ctx.ws_ptr, ctx.ws_bytes, out_ptr, ctx.stream)
         N_.check(rc, "cdn_codenet_pointwise_mixed_forward")
 
     recompute_pw1 = True      # A/B switch (tools/e2e_native_bench.py --no-recompute)
@@ -430,7 +432,7 @@ class FusedBackbone:
         rc = fn(
             x_ptr, x_q, N, cin, H, W, ld_x, Wt["w"].data_ptr(), Wt["codes"].data_ptr(), Wt["scale"].data_ptr(),
             Wt["colsum"].data_ptr(), Wt["bias"].data_ptr(), am[0], am[1], am[2], C, w.data_ptr(), b.data_ptr(), ld_out,
-            ao[0], ao[1], ao[2], ao[3], ao[4], ao[5], ctx.ws_ptr, ctx.ws_bytes, out.data_ptr(), ctx.stream)
+            ao[0], ao[1], ao[2], ao[3], ao[4], ao[5] | Wt.get("wflag", 0), ctx.ws_ptr, ctx.ws_bytes, out.data_ptr(), ctx.stream)
         N_.check(rc, "cdn_codenet_pwdw_s2_forward")
 
     def _dw_raw(self, ctx, a_ptr, a_q, a_gen, N, C, H, W, stride, ld_in, w, b, act, out, ld_out):

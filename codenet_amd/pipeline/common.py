@@ -152,16 +152,24 @@ WCODES_KB = 0x800           # CDN_X_WCODES_KB
 DEFER_RANGE = 0x1000        # CDN_X_DEFER_RANGE
 
 
+# CDN_W_CODES_8BIT: the int8 weight codes of the call may leave [-8, 8] (W8A8) -- defined once, beside the predicate
+from ..portable_quantizer.quant_modules import W_CODES_8BIT      # noqa: E402,F401
+
+
 PHASE_SCALE, PHASE_GATHER, PHASE_POINTWISE = 0x2000, 0x4000, 0x8000      # CDN_X_PHASE_*
 
 
 def stage_int8_codes(convbn, kblocked=True):
     """(i8 triple or None, flag) for the pointwise conv of a fused stage: the int8 form of the folded weights, with the
     k-blocked copy behind the codes -- and CDN_X_WCODES_KB to OR into the stage call's layout argument -- where the
-    library has a use for it (long-K stages: cdn_codenet_wcodes_kb_columns)."""
+    library has a use for it (long-K stages: cdn_codenet_wcodes_kb_columns).  Codes wider than 4 bits (W8A8): the flag
+    is CDN_W_CODES_8BIT and no copy is built -- the streaming kernel that reads it is a 4-bit kernel."""
     from .. import _native as N_
     lib = N_.lib()
     conv = convbn.conv
+    if convbn.int8_width_flag():
+        i8 = convbn.folded_int8()
+        return i8, (convbn.int8_width_flag() if i8 is not None else 0)
     cols = lib.cdn_codenet_wcodes_kb_columns(conv.in_channels, conv.out_channels) if kblocked else 0
     if cols:
         i8 = convbn.folded_int8_kblocked(cols, lib.cdn_codenet_wcodes_kb_offset(conv.in_channels, conv.out_channels))

@@ -68,12 +68,13 @@ class FusedHeads:
             i8 = self.int8_pointwise
             return [
                 dict(kind="pw", w=w1.reshape(w1.size(0), -1), bias=b1, ep=None, relu=1,
-                     i8=mod.quant_convbn1.folded_int8() if i8 else None, act=mod.quant_act1[1]),
+                     i8=mod.quant_convbn1.folded_int8() if i8 else None, act=mod.quant_act1[1],
+                     wq=mod.quant_convbn1),
                 dict(kind="dw", w=w2.reshape(w2.size(0), 9), bias=b2, ep=None, relu=1,
                      act=mod.quant_act3[1]),
                 dict(kind="pw", w=mod.quant_conv.quantized_weight().reshape(mod.quant_conv.out_channels, -1),
                      bias=mod.quant_conv.bias, ep=None, relu=0,
-                     i8=mod.quant_conv.int8_form() if i8 else None, act=None)]
+                     i8=mod.quant_conv.int8_form() if i8 else None, act=None, wq=mod.quant_conv)]
         if isinstance(mod, nn.Conv2d):
             return [dict(kind="pw", w=mod.weight.reshape(mod.out_channels, -1), bias=mod.bias, ep=None,
                          relu=0, i8=None, act=None)]
@@ -107,7 +108,9 @@ class FusedHeads:
                 colsum=torch.cat([l_["i8"][2].reshape(-1) for l_ in firsts], 0).contiguous(),
                 bias=(torch.cat([l_["bias"].reshape(-1) for l_ in firsts], 0).contiguous()
                       if all(l_["bias"] is not None for l_ in firsts) else None),
-                omap=(torch.arange(64 * nh, dtype=torch.int32, device=dev) % 64).contiguous())
+                omap=(torch.arange(64 * nh, dtype=torch.int32, device=dev) % 64).contiguous(),
+                # one launch for all heads: the 8-bit form as soon as one head's codes need it (it is exact on narrower ones)
+                wflag=max(l_["wq"].int8_width_flag() for l_ in firsts))
             if cat["bias"] is None and any(l_["bias"] is not None for l_ in firsts):
                 return None
             self._first = (key, cat)
@@ -176,7 +179,8 @@ class FusedHeads:
             rc = lib.cdn_codenet_pointwise_nhwc_forward(
                 a.data_ptr(), aq, m, layer["w"].shape[1], layer["w"].shape[0], 0, 0, ptr(layer["w"]),
                 ptr(i8[0]), ptr(i8[1]), ptr(i8[2]), ptr(layer["bias"]), ptr(ep[0]), ptr(ep[1]),
-                layer["relu"], *act_args(layer["act"]), ws_ptr, ws_bytes, out.data_ptr(), stream)
+                layer["relu"] | (layer["wq"].int8_width_flag() if layer["i8"] is not None else 0),
+                *act_args(layer["act"]), ws_ptr, ws_bytes, out.data_ptr(), stream)
             ops._toc(rec)
             N_.check(rc, "cdn_codenet_pointwise_nhwc_forward")
 
@@ -215,7 +219,7 @@ class FusedHeads:
             rec = ops._tic("head_pw", (C, 64 * nh, M))
             rc = lib.cdn_codenet_heads_pointwise_forward(
                 r.data_ptr(), r_qstate, M, C, nh, ptr(first["w"]), ptr(first["codes"]), ptr(first["scale"]),
-                ptr(first["colsum"]), ptr(first["bias"]), 1, P(*[a_.x_min.data_ptr() for a_ in acts]),
+                ptr(first["colsum"]), ptr(first["bias"]), 1 | first["wflag"], P(*[a_.x_min.data_ptr() for a_ in acts]),
                 P(*[a_.x_max.data_ptr() for a_ in acts]), P(*[a_._device_state(r.device).data_ptr() for a_ in acts]),
                 bits, mom, running, P(*wptr), wbytes, ptr(first["omap"]), B["y1_all"].data_ptr(), M * 64, stream)
             ops._toc(rec)
@@ -278,12 +282,12 @@ class FusedHeads:
                     q2 = l2["act"]._device_state(r.device).data_ptr()
                     i8 = l3["i8"]
                     rec = ops._tic("head_tail_small", (C, l3["w"].shape[0], 4 * M))
-                    rc = lib.cdn_codenet_head_tail_small_forward(
+                    rc = lib.cdn_codenet_head_tail_small_w_forward(
                         y1buf.data_ptr(), q1, Nb, C, Hs, Ws, ptr(l2["w"]), ptr(l2["bias"]), q2, ptr(i8[0]),
                         ptr(i8[1]), ptr(i8[2]), ptr(l3["bias"]), l3["w"].shape[0], B["out"][name].data_ptr(),
-                        stream)
+                        l3["wq"].int8_width(), stream)
                     ops._toc(rec)
-                    N_.check(rc, "cdn_codenet_head_tail_small_forward")
+                    N_.check(rc, "cdn_codenet_head_tail_small_w_forward")
                     outs[name] = B["out"][name]
                     continue
                 rec = ops._tic("head_dw", (C, 2 * Hs, 2 * Ws))
@@ -330,7 +334,7 @@ class FusedHeads:
         """The heads on the BYTE CODES of the last deform stage (``FrozenHotPath.forward_codes``), every QuantAct
         frozen: per head the int8 pointwise kernel on codes (cdn_codenet_pointwise_q8_forward: exact integer sums,
         the codes of quant_act1 written as bytes) and the row-streaming tail reading those bytes
-        (cdn_codenet_head_tail_small_q8_forward); no range passes, no fp32 copy of the stage output or of y1.
+        (cdn_codenet_head_tail_small_q8_w_forward); no range passes, no fp32 copy of the stage output or of y1.
         Same values as ``__call__`` on the expanded codes with the same frozen states (the first 1x1 conv is the same
         integer sum; the tail decodes a code to the value its fp32 form fake-quantises to).  `overflow`: an OverflowFlags
         (word 2i: head i's y1 codes, word 2i + 1: its tail) or an int32 tensor (one word for everything).  covered: what
@@ -397,11 +401,11 @@ class FusedHeads:
                     1, q1, y8.data_ptr(), None, of1, st.cuda_stream)
                 N_.check(rc, "cdn_codenet_pointwise_q8_forward")
                 i8 = l3["i8"]
-                rc = lib.cdn_codenet_head_tail_small_q8_forward(
+                rc = lib.cdn_codenet_head_tail_small_q8_w_forward(
                     y8.data_ptr(), q1, Nb, 64, Hs, Ws, ptr(l2["w"]), ptr(l2["bias"]), q2, ptr(i8[0]), ptr(i8[1]),
                     ptr(i8[2]), ptr(l3["bias"]), l3["w"].shape[0], B["out"][name].data_ptr(), of2,
-                    st.cuda_stream)
-                N_.check(rc, "cdn_codenet_head_tail_small_q8_forward")
+                    l3["wq"].int8_width(), st.cuda_stream)
+                N_.check(rc, "cdn_codenet_head_tail_small_q8_w_forward")
         for sd in forked:
             main.wait_stream(sd)
         return B["out"]

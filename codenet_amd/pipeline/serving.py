@@ -228,7 +228,7 @@ class FrozenHotPath:
         self.seq = deconv_layers
         for st in self.stages:
             if st[0].quant_conv_channel_bn.folded_int8() is None:
-                raise NotImplementedError("FrozenHotPath needs per-channel symmetric <= 4-bit pointwise weights")
+                raise NotImplementedError("FrozenHotPath needs per-channel symmetric <= 8-bit pointwise weights")
         self._bufs = None
 
     @staticmethod

@@ -75,6 +75,9 @@ def refresh_in_place(old, new):
     return new
 
 
+W_CODES_8BIT = 0x20000      # CDN_W_CODES_8BIT (include/codenet_dcn.h)
+
+
 class _WeightQuantizer:
     """Shared weight fake-quantisation of the three Quant*Conv modules + an inference cache."""
 
@@ -112,11 +115,28 @@ class _WeightQuantizer:
                                     self.weight_percentile)
 
     def _int8_ok(self, kernel_size, groups):
-        return not (self.full_precision_flag or not self.per_channel or self.weight_bit > 4
+        """INFERENCE: this layer has an integer form for the int8 matrix cores -- per-channel symmetric, 1x1, groups 1,
+        at most 8 bits (the codes are one byte).  Above 4 bits the codes no longer satisfy |q| <= 8, and every call that
+        hands them to the library says so with int8_width_flag()."""
+        return not (self.full_precision_flag or not self.per_channel or self.weight_bit > 8
                     or self.quant_mode != "symmetric" or tuple(kernel_size) != (1, 1) or groups != 1)
 
+    def _int8_train_ok(self, kernel_size, groups):
+        """TRAINING: the native QAT stage may sum integer codes -- _int8_ok at <= 4 bits (the scale recovery of the
+        training kernels knows the grids m = 1 ... 8 only; wider rows would come back as NaN)."""
+        return self._int8_ok(kernel_size, groups) and self.weight_bit <= 4
+
+    def int8_width_flag(self):
+        """CDN_W_CODES_8BIT (include/codenet_dcn.h) when the codes of this layer may leave [-8, 8], else 0: OR-ed into the
+        `relu` / `x_nhwc` argument of the entries that take them."""
+        return W_CODES_8BIT if self.weight_bit > 4 else 0
+
+    def int8_width(self):
+        """The w_bits argument of the head-tail entries: 4 (|q| <= 8) or 8."""
+        return 8 if self.weight_bit > 4 else 4
+
     def _int8_codes(self, w):
-        """Integer form of per-channel symmetric <= 4-bit 1x1 weights for the int8-MFMA pointwise
+        """Integer form of per-channel symmetric <= 8-bit 1x1 weights for the int8-MFMA pointwise
         kernel: (codes int8 [Co, round_up(C,64)] zero padded, scale fp32 [Co] with w' = codes / scale,
         column sums int32 [Co]).  Same expressions as SymmetricQuantFunction.forward
         (quant_utils.py:207-225)."""
@@ -303,7 +323,7 @@ class Quant_Conv2d(Module, _WeightQuantizer):
 
     def int8_form(self):
         """Integer form of the fake-quantised 1x1 weights (see _int8_codes); None when this layer is
-        not per-channel symmetric <= 4 bit."""
+        not per-channel symmetric <= 8 bit."""
         if not self._int8_ok(self.kernel_size, self.groups):
             return None
         return self._cached_i8((self.weight,), lambda: self._int8_codes(self.weight))
@@ -351,7 +371,7 @@ class QuantBnConv2d(Module, _WeightQuantizer):
 
     def folded_int8(self):
         """Integer form of the folded, fake-quantised 1x1 weights for the int8-MFMA pointwise kernel
-        (see _int8_codes); None when this layer is not per-channel symmetric <= 4 bit."""
+        (see _int8_codes); None when this layer is not per-channel symmetric <= 8 bit."""
         if not self._int8_ok(self.conv.kernel_size, self.conv.groups):
             return None
 
@@ -519,7 +539,7 @@ class QuantDeformConvWithOffsetScaleBoundPositive(Module):
             w_dw = pre_w[1] if pre_w[1] is not None else self.quant_deform_conv.quantized_weight()
             return codenet_stage(x, w_sc, self.quant_conv_scale.bias, w_dw, w, b, bound.min_val, bound.max_val,
                                  self.quant_act[1], self.quant_identity_deform, want_range, x_up,
-                                 cb._int8_ok(cb.conv.kernel_size, cb.conv.groups))
+                                 cb._int8_train_ok(cb.conv.kernel_size, cb.conv.groups))
         s = self.quant_act(self.quant_conv_scale(x))
         dc = self.quant_deform_conv
         if (x.is_cuda and x.dtype == torch.float32 and s.shape[1] == 1

@@ -529,6 +529,10 @@ int64_t cdn_codenet_wcodes_kb_offset(int64_t C, int64_t Co);
  * the launch's LDS size) that the runtime keeps resident per CU.  0: no such kernel for this Co; negative: the runtime's
  * error code. */
 int cdn_codenet_pwi8s_resident_workgroups(int64_t Co);
+/* Diagnostics / tests: the tile of the tiled int8 pointwise kernel for a dense [M][C] -> [M][Co] launch, as
+ * rows * 1000 + columns (32128, 64128, 64064, 128064; 0: bad size).  The choice does not depend on the width of the
+ * codes; launches that take the streaming kernel (4-bit codes with CDN_X_WCODES_KB) are not described by it. */
+int cdn_codenet_pointwise_i8_tile(int64_t M, int64_t C, int64_t Co);
 /* | CDN_X_DEFER_RANGE and the phase bits (round 5; SURVEY.md section 8e, collective 3 -- the multi-process parity mode in
  * which R ranks x B images track the ranges of ONE R*B-image run; the reference's only multi-GPU mechanism,
  * lib/models/data_parallel.py:64-84, scatters one batch and so has batch-global ranges by construction): the stage call
@@ -547,6 +551,29 @@ int cdn_codenet_pwi8s_resident_workgroups(int64_t Co);
 #define CDN_X_PHASE_GATHER 0x4000
 #define CDN_X_PHASE_POINTWISE 0x8000
 #define CDN_X_PHASE_MASK 0xE000
+/* | CDN_W_CODES_8BIT (W8A8): the int8 weight codes handed to the call (`w_pw_codes` / `w_codes`) may hold ANY int8 value
+ * (per-channel symmetric weights of up to 8 bits, q in [-128, 127]).  A launcher cannot see the width of device bytes, so
+ * the caller states it, per call (no library state); the flag is OR-ed into
+ *   `x_nhwc` of cdn_codenet_stage_fused_forward,
+ *   `relu`   of cdn_codenet_pointwise_nhwc_forward / _mixed_forward / _mixed_forward_n and
+ *            cdn_codenet_heads_pointwise_forward (the epilogue sees relu without the flag),
+ *   `running` of cdn_codenet_pwdw_s2_forward / _apply (for the range-only pass of the 1x1 conv inside _forward);
+ * the head tail, which has no int argument, has sibling entries with a `w_bits` argument
+ * (cdn_codenet_head_tail_small_w_forward / cdn_codenet_head_tail_small_q8_w_forward).
+ * WITHOUT the flag these entries assume |q| <= 8 (<= 4-bit codes), as before the flag existed: the kernels that split the
+ * activation code into two nibble planes multiply the high plane with 16 * q held in a byte, and an 8-bit code wraps
+ * silently.  With it the same kernels keep the high plane's sums in an accumulator of their own and form
+ * acc_lo + 16 * acc_hi in int32 (exact for C <= 4096, which is checked); long-K stages take the tiled
+ * kernel instead of the streaming one (CDN_X_WCODES_KB is accepted and its copy not read).  Results with the flag on
+ * <= 4-bit codes are those without it, bit for bit.
+ * Entries that NEVER needed the flag, because their arithmetic does not depend on the width of the weight byte -- "4-bit"
+ * in their descriptions named the network they were written for, not a limit: the byte-code entries of the serving mode
+ * (cdn_codenet_pointwise_q8[_strided]_forward, cdn_codenet_dwpw_q8_forward, cdn_codenet_stage_frozen[_chained]_forward: int8
+ * activation codes x int8 weight codes, one product plane), the recomputing kernel of cdn_codenet_pwdw_s2_forward / _apply
+ * (the 16 multiplies the SUM of the high plane) and the bf16 x 3 kernels behind a_gen / final-valued inputs of the pointwise entries (|q| <= 128
+ * is exact in bf16).  The training entries (cdn_codenet_pointwise_i8_*, cdn_codenet_weight_prep*) stay at <= 4 bits: their
+ * scale recovery knows the grids m = 1 ... 8 only.  (0x10000 stays an invalid value of x_nhwc.) */
+#define CDN_W_CODES_8BIT 0x20000
 int cdn_quantact_commit_range(float *x_min, float *x_max, void *state, const float *range, int bits, double momentum,
                               int running, void *stream);
 int cdn_codenet_stage_fused_forward(
@@ -845,6 +872,19 @@ int cdn_codenet_head_tail_small_q8_forward(const signed char *y1_codes, const vo
                                            const void *y2_qstate, const signed char *w_codes, const float *w_scale,
                                            const int *w_colsum, const float *bias, int64_t classes, float *out_nchw,
                                            unsigned *overflow, void *stream);
+/* The two tails with the width of w_codes stated by the caller (see CDN_W_CODES_8BIT): w_bits = 4 is exactly the entry
+ * without the argument (|q| <= 8), w_bits = 8 admits any int8 code; other values: CDN_ERR_ARG.  Same results as the
+ * unfused schedule on the same codes, bit for bit. */
+int cdn_codenet_head_tail_small_w_forward(const float *y1, const void *y1_qstate, int64_t N, int64_t C, int64_t Hs,
+                                          int64_t Ws, const float *w_dw, const float *b_dw, const void *y2_qstate,
+                                          const signed char *w_codes, const float *w_scale, const int *w_colsum,
+                                          const float *bias, int64_t classes, float *out_nchw, int w_bits,
+                                          void *stream);
+int cdn_codenet_head_tail_small_q8_w_forward(const signed char *y1_codes, const void *y1_qstate, int64_t N, int64_t C,
+                                             int64_t Hs, int64_t Ws, const float *w_dw, const float *b_dw,
+                                             const void *y2_qstate, const signed char *w_codes, const float *w_scale,
+                                             const int *w_colsum, const float *bias, int64_t classes, float *out_nchw,
+                                             unsigned *overflow, int w_bits, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The backbone's remaining layer types (lib/models/networks/

@@ -24,6 +24,11 @@ BUDGET = {
     "pwi8_kernelILi64ELi64ELi2ELb1": 128,         # Co <= 64 at large M: stage 2, layer 1, heads
     "scale_nchw_kernel": 128, "scale_nhwc_kernelILb1": 128, "unpack_kernelILb1": 128,
     "pwd3_kernelILi2": 256, "pwd3_kernelILi4": 256,   # streaming pointwise: two waves per SIMD
+    # 8-bit weight codes (W8A8): a second accumulator set for the high nibble plane -- the 128-column tiles at three
+    # workgroups per CU (160 / 148 VGPRs when written), the others at four (88 / 96 / 96)
+    "pwi8w_kernelILi64ELi128ELi2ELb1": 168, "pwi8w_kernelILi128ELi64ELi4ELb1": 168,
+    "pwi8w_kernelILi32ELi128ELi1ELb1": 128, "pwi8w_kernelILi64ELi64ELi2ELb1": 128,
+    "pwi8h_kernelILi2ELi8": 128, "pwi8h_kernelILi3ELi8": 128, "pwi8h_kernelILi4ELi8": 128,
 }
 # SGPR spills go to VGPR lanes (v_writelane / v_readlane, no memory): tolerated up to this many where listed
 SGPR_SPILLS_OK = {"pwd3_kernelILi4": 6}     # round 4: the window cursors of the unit-entry conv (228 VGPRs); round 5: + the NaN flag's mask

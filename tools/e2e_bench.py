@@ -32,9 +32,10 @@ def main():
     ap.add_argument("--fp32", action="store_true")
     ap.add_argument("--w2", action="store_true")
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--w-bit", type=int, default=4, help="weight width of the quantised model (8: W8A8)")
     a = ap.parse_args()
     dev = "cuda"
-    model = harness.create_model(w2=a.w2, quantize=not a.fp32).to(dev)
+    model = harness.create_model(w2=a.w2, quantize=not a.fp32, w_bit=a.w_bit).to(dev)
     x = torch.randn(a.batch, 3, a.res, a.res, device=dev)
     fused = pipeline.FusedHotPath(model.deconv_layers)
     fheads = pipeline.FusedHeads({h: getattr(model, h) for h in model.heads})

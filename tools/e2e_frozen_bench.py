@@ -61,9 +61,10 @@ def main():
     ap.add_argument("--ab-heads", type=int, default=0, metavar="PAIRS",
                     help="A/B: the heads on the byte codes of the last stage (the plan's third member) against the heads on "
                          "the expanded codes (FusedHeads(small_tail=False)), PAIRS interleaved pairs of the captured graphs")
+    ap.add_argument("--w-bit", type=int, default=4, help="weight width of the quantised model (8: W8A8)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    model = harness.create_model(heads={"hm": a.classes, "wh": 2, "reg": 2}, quantize=True, w2=a.w2).to(dev)
+    model = harness.create_model(heads={"hm": a.classes, "wh": 2, "reg": 2}, quantize=True, w2=a.w2, w_bit=a.w_bit).to(dev)
     twin = copy.deepcopy(model) if a.ab_heads else None
     model.merge_frozen_params = not a.no_merge_params
     model.enable_fused()

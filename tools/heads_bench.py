@@ -52,9 +52,10 @@ def main():
     ap.add_argument("--ab", type=int, default=0, metavar="PAIRS",
                     help="A/B of the hm head alone: FusedHeads(small_tail=True), the fused tail, against small_tail=False, "
                          "the unfused schedule (depthwise store -> int8 pointwise -> unpack), PAIRS interleaved pairs")
+    ap.add_argument("--w-bit", type=int, default=4, help="weight width of the quantised model (8: W8A8)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    model = harness.create_model(heads={"hm": a.classes, "wh": 2, "reg": 2}, quantize=not a.fp32).to(dev)
+    model = harness.create_model(heads={"hm": a.classes, "wh": 2, "reg": 2}, quantize=not a.fp32, w_bit=a.w_bit).to(dev)
     feat = pipeline.make_input(a.batch, a.res, device=dev)
     path = pipeline.FusedHotPath(model.deconv_layers)
     if a.ab:

@@ -1,5 +1,6 @@
 """Isolated timing of the pointwise kernels at the ShuffleNetV2 unit shapes (GPU only):
-python tools/pw_bench.py [M C Co lda]  -- modes: final / single-state / mixed input, dense or mapped output."""
+python tools/pw_bench.py [M C Co lda] [--w-bit 4|8]  -- modes: final / single-state / mixed input, dense or mapped output.
+--w-bit 8: weight codes over the whole int8 range, handed over with CDN_W_CODES_8BIT (W8A8)."""
 import json
 import os
 import sys
@@ -38,6 +39,15 @@ def graph_time(run, reps=20):
 
 def main():
     global stream
+    w_bit = 4
+    if "--w-bit" in sys.argv:
+        i = sys.argv.index("--w-bit")
+        w_bit = int(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+    if w_bit not in (4, 8):
+        raise SystemExit("--w-bit 4 or 8")
+    from codenet_amd.pipeline import W_CODES_8BIT
+    wflag, qmax = (W_CODES_8BIT, 128) if w_bit == 8 else (0, 8)
     M, C, Co, lda = (int(v) for v in sys.argv[1:5]) if len(sys.argv) > 4 else (262144, 116, 58, 116)
     dev = torch.device("cuda", 0)
     lib = N_.lib()
@@ -48,7 +58,7 @@ def main():
     g = torch.Generator().manual_seed(0)
     a = torch.randn(M, lda, generator=g).to(dev)
     cpad = (C + 63) // 64 * 64
-    q = torch.randint(-8, 8, (Co, C), generator=g)
+    q = torch.randint(-qmax, qmax, (Co, C), generator=g)
     codes = torch.zeros(Co, cpad, dtype=torch.int8)
     codes[:, :C] = q.to(torch.int8)
     codes = codes.to(dev)
@@ -75,7 +85,7 @@ def main():
         def run():
             rc = lib.cdn_codenet_pointwise_mixed_forward_n(
                 a.data_ptr(), aq, ag, ng, M, C, Co, lda, ld_o, w.data_ptr(), codes.data_ptr(), scale.data_ptr(),
-                colsum.data_ptr(), bias.data_ptr(), None, None, 1, om, xmin.data_ptr(), xmax.data_ptr(),
+                colsum.data_ptr(), bias.data_ptr(), None, None, 1 | wflag, om, xmin.data_ptr(), xmax.data_ptr(),
                 st.data_ptr(), 8, 0.99, 1, wp, wb, out.data_ptr(), stream)
             N_.check(rc, "pw")
         res[name] = graph_time(run)
@@ -100,6 +110,7 @@ def main():
                 d = sd[:, i + 1] - sd[:, i]
                 print("  %-28s mean %.2f  p90 %.2f us" % (nm, d.mean(), np.percentile(d, 90)))
     res["shape"] = [M, C, Co, lda]
+    res["w_bit"] = w_bit
     res["MB"] = round((M * C * 4 + M * Co * 4) / 1e6, 1)
     print(json.dumps(res))
 
