@@ -222,6 +222,18 @@ _SIGNATURES = {
     "cdn_codenet_stem_fp32_bn_relu_backward_sums": (_i, [_vp] * 10 + [_i64] * 4 + [_vp, ctypes.c_size_t, _vp]),
     "cdn_codenet_stem_fp32_wgrad_workspace_bytes": (ctypes.c_size_t, [_i64] * 3 + [_i]),
     "cdn_codenet_stem_fp32_wgrad": (_i, [_vp, _i] + [_vp] * 9 + [_i64] * 4 + [_i, _i, _vp, ctypes.c_size_t, _vp]),
+    "cdn_eval_append": (_i, [_vp, _vp] + [_i64] * 4 + [_vp, _vp, _i64, _i64, _i, _vp, _vp]),
+    "cdn_eval_append_host": (_i, [_vp, _vp] + [_i64] * 4 + [_vp, _vp, _i64, _i64, _i, _vp]),
+    "cdn_eval_sort_keys": (_i, [_vp, _vp] + [_i64] * 3 + [_i, _vp, _vp, _vp]),
+    "cdn_eval_sort_keys_host": (_i, [_vp, _vp] + [_i64] * 3 + [_i, _vp, _vp]),
+    "cdn_eval_match_voc": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 3 + [_d] + [_vp] * 3 + [_vp]),
+    "cdn_eval_match_voc_host": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 3 + [_d] + [_vp] * 3),
+    "cdn_eval_accumulate_voc": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 5 + [_i64] + [_vp] * 6 + [_vp]),
+    "cdn_eval_accumulate_voc_host": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 5 + [_i64] + [_vp] * 6),
+    "cdn_eval_match_coco": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 4 + [_i64] + [_vp] * 7 + [_vp]),
+    "cdn_eval_match_coco_host": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 4 + [_i64] + [_vp] * 7),
+    "cdn_eval_accumulate_coco": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 9 + [_vp]),
+    "cdn_eval_accumulate_coco_host": (_i, [_vp, _vp] + [_i64] * 3 + [_vp] * 9),
     "cdn_profile_enable": (_i, [_i]),
     "cdn_profile_read": (_i, [_i, _vp, _vp, _vp]),
 }

@@ -687,6 +687,7 @@ def capture_process_scales(model, images, n_scales, flip_test, metas, scales, nu
     replay.buffers = bufs
     replay.meta = meta
     replay.raw = rawres
+    replay.graph = graph      # graph.replay() alone leaves the results in replay.raw with no host copy (evalio.DeviceResults)
     return replay
 
 

@@ -1534,6 +1534,84 @@ int cdn_codenet_stem_fp32_wgrad(const float *g, int masked, const float *y0, con
                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Detection scoring: VOC07 AP per class and COCO's bbox precision / recall arrays from a detection table that stays on
+ * the device.  codenet_eval.hip + cdn_eval.h; Python: codenet_amd/evalio.py (DeviceResults, GroundTruth, voc_eval_device,
+ * coco_eval).  DESIGN.md section 7.4e is the contract; tests/coco_eval_ref.py restates the COCO half in numpy.
+ * All box arithmetic is float64, every operation rounded on its own; what crosses lanes is an integer count or a
+ * maximum, so every entry is a pure function of its inputs bit for bit.  Every entry has a `_host` twin without the
+ * stream argument that runs the same text (cdn_eval.h) on HOST memory with no HIP call.  One launch per entry, no host
+ * synchronisation.  Argument errors are returned before any HIP call.
+ *
+ *   det    [n_images][cap][6] float64: x1 y1 x2 y2 score class (VOC) or x y w h score class (COCO), class 0-based
+ *   count  [n_images] int32 rows in use, zeroed by the caller before the first append
+ *   flag   [1] int32, zeroed by the caller: bit 0 an append met more than cap rows (the rows beyond are NOT stored and
+ *          the accumulate entries hand the word back: the caller must treat it as an error), bit 1 a score that the
+ *          sort key cannot order (NaN, or |score| >= 2^31 / 100 in COCO mode)
+ *   gt_box [total_gt][4] float64 (x1 y1 x2 y2 / x y w h), gt_area [total_gt], gt_flag [total_gt] int32 (bit 0: difficult
+ *          / iscrowd), gt_off [n_images * classes + 1] int32: the rows of (image, class) are gt_off[i * classes + c] ..
+ * cap <= 1024, classes <= 256, n_images * cap < 2^25 (CDN_ERR_UNSUPPORTED beyond).
+ *
+ * cdn_eval_append: the result block of cdn_ctdet_merge_scales (boxes [B][classes][R][5] float32, rows_out [B][classes])
+ *   behind the rows already in slots image_slot .. image_slot + B - 1, class-major.  coco != 0: w = x2 - x1 and
+ *   h = y2 - y1 in float32, then every number v becomes rint((double)v * 100.0) / 100.0 = float("%.2f" % v).
+ * cdn_eval_sort_keys: keys [n_images * cap] int64 = (class << 32) | inverted orderable score; rows behind count sort
+ *   last.  An ascending STABLE sort of the keys (the caller's: torch.sort) orders every class by descending score with
+ *   ties in (image, row) order; keys_sorted / perm below are its two results.
+ * cdn_eval_match_voc: voc_eval.py:95-207 per (image, class), one wave each: tp / fp [n_images * cap] uint8 per table row.
+ *   seen [total_gt] uint8 scratch.
+ * cdn_eval_accumulate_voc: per class rec / prec [n_images * cap] at the sorted positions, env (the envelope) and terms
+ *   [n_images * cap + classes] scratch; thresholds [n_thr] the recall points (np.arange(0, 1.1, 0.1)).
+ *   out [4 * classes + 2] float64: ap_07 [classes], ap_area [classes] (numpy's pairwise summation order), npos [classes],
+ *   the first sorted position of every class [classes + 1], the flag word.
+ * cdn_eval_match_coco: COCOeval.evaluateImg for bbox per (image, category), one wave each, lanes = 10 IoU thresholds x 4
+ *   area ranges (area_rng [4][2]).  dtm / dtig [40][n_images * cap] uint8 (lane = threshold * 4 + area range) per table
+ *   row, rank [n_images * cap] int32 within (image, category), gt_nonign [n_images * classes][4] int32; gtm [40][total_gt]
+ *   uint8 scratch.  The first 100 ranked detections take part.  The D x G IoU matrix lives in LDS when D * G <= 4096 and
+ *   is formed on the fly otherwise: the same bits.  No cap on G.
+ * cdn_eval_accumulate_coco: COCOeval.accumulate: precision [10][101][classes][4][3], recall [10][classes][4][3]
+ *   (maxDets 1, 10, 100; -1 where no ground truth counts), rec_thrs [101]; flag_out [1] float64 = the flag word.
+ * ---------------------------------------------------------------------------------------- */
+int cdn_eval_append(const float *boxes, const int32_t *rows_out, int64_t B, int64_t classes, int64_t R, int64_t image_slot,
+                    double *det, int32_t *count, int64_t n_images, int64_t cap, int coco, int32_t *flag, void *stream);
+int cdn_eval_append_host(const float *boxes, const int32_t *rows_out, int64_t B, int64_t classes, int64_t R,
+                         int64_t image_slot, double *det, int32_t *count, int64_t n_images, int64_t cap, int coco,
+                         int32_t *flag);
+int cdn_eval_sort_keys(const double *det, const int32_t *count, int64_t n_images, int64_t cap, int64_t classes, int coco,
+                       int64_t *keys, int32_t *flag, void *stream);
+int cdn_eval_sort_keys_host(const double *det, const int32_t *count, int64_t n_images, int64_t cap, int64_t classes, int coco,
+                            int64_t *keys, int32_t *flag);
+int cdn_eval_match_voc(const double *det, const int32_t *count, int64_t n_images, int64_t cap, int64_t classes,
+                       const double *gt_box, const int32_t *gt_flag, const int32_t *gt_off, double ovthresh,
+                       unsigned char *seen, unsigned char *tp, unsigned char *fp, void *stream);
+int cdn_eval_match_voc_host(const double *det, const int32_t *count, int64_t n_images, int64_t cap, int64_t classes,
+                            const double *gt_box, const int32_t *gt_flag, const int32_t *gt_off, double ovthresh,
+                            unsigned char *seen, unsigned char *tp, unsigned char *fp);
+int cdn_eval_accumulate_voc(const int64_t *keys_sorted, const int64_t *perm, int64_t n_images, int64_t cap, int64_t classes,
+                            const unsigned char *tp, const unsigned char *fp, const int32_t *gt_flag, const int32_t *gt_off,
+                            const double *thresholds, int64_t n_thr, const int32_t *flag, double *rec, double *prec,
+                            double *env, double *terms, double *out, void *stream);
+int cdn_eval_accumulate_voc_host(const int64_t *keys_sorted, const int64_t *perm, int64_t n_images, int64_t cap,
+                                 int64_t classes, const unsigned char *tp, const unsigned char *fp, const int32_t *gt_flag,
+                                 const int32_t *gt_off, const double *thresholds, int64_t n_thr, const int32_t *flag,
+                                 double *rec, double *prec, double *env, double *terms, double *out);
+int cdn_eval_match_coco(const double *det, const int32_t *count, int64_t n_images, int64_t cap, int64_t classes,
+                        const double *gt_box, const double *gt_area, const int32_t *gt_flag, const int32_t *gt_off,
+                        int64_t total_gt, const double *iou_thrs, const double *area_rng, unsigned char *gtm,
+                        unsigned char *dtm, unsigned char *dtig, int32_t *rank, int32_t *gt_nonign, void *stream);
+int cdn_eval_match_coco_host(const double *det, const int32_t *count, int64_t n_images, int64_t cap, int64_t classes,
+                             const double *gt_box, const double *gt_area, const int32_t *gt_flag, const int32_t *gt_off,
+                             int64_t total_gt, const double *iou_thrs, const double *area_rng, unsigned char *gtm,
+                             unsigned char *dtm, unsigned char *dtig, int32_t *rank, int32_t *gt_nonign);
+int cdn_eval_accumulate_coco(const int64_t *keys_sorted, const int64_t *perm, int64_t n_images, int64_t cap, int64_t classes,
+                             const unsigned char *dtm, const unsigned char *dtig, const int32_t *rank,
+                             const int32_t *gt_nonign, const double *rec_thrs, const int32_t *flag, double *precision,
+                             double *recall, double *flag_out, void *stream);
+int cdn_eval_accumulate_coco_host(const int64_t *keys_sorted, const int64_t *perm, int64_t n_images, int64_t cap,
+                                  int64_t classes, const unsigned char *dtm, const unsigned char *dtig, const int32_t *rank,
+                                  const int32_t *gt_nonign, const double *rec_thrs, const int32_t *flag, double *precision,
+                                  double *recall, double *flag_out);
+
+/* ------------------------------------------------------------------------------------------
  * Optional per-kernel timing with HIP events on the launch stream (thread-local; off by default).
  * While enabled, each kernel of cdn_codenet_stage_fused_forward / cdn_codenet_unpack_nchw records
  * an event pair.  cdn_profile_read synchronises the recorded events and returns up to max_records

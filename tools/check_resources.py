@@ -117,6 +117,13 @@ BUDGET_UNITS_FP32_TRAIN = {"unit32_dw_fwd_kernel": 64, "unit32_apply_kernel": 32
 # codenet_stem_train.hip's 4 x 28 sums beside the 27-value patch (160, three waves per SIMD); no scratch, no spills
 BUDGET_STEM_FP32_TRAIN = {"stem32_pool_fwd_kernel": 64, "stem32_pool_bwd_kernel": 96, "bn_bwd1_kernelILi1": 64,
                           "stem32_wgrad_kernel": 168}
+# codenet_eval.hip (detection scoring): float64 box arithmetic in small launches that hide latency
+# with occupancy -- eight waves per SIMD (64 VGPRs; 23-60 when written).  The VOC accumulate keeps the explicit stack of
+# numpy's pairwise summation (48 frames, thread 0 only, once per class) in private memory: 1360 bytes, no register spills
+BUDGET_EVAL = {"eval_append_kernel": 64, "eval_keys_kernel": 64, "eval_match_voc_kernel": 64, "eval_match_coco_kernel": 64,
+               "eval_accumulate_voc_kernel": 64, "eval_accumulate_coco_kernel": 64}
+SCRATCH_OK = {"eval_accumulate_voc_kernel": 2048}
+
 
 def kernel_resources(src="codenet_fused.hip", extra=()):
     with tempfile.TemporaryDirectory() as tmp:
@@ -153,6 +160,7 @@ def check():
     for src, extra, budget in (("codenet_stage.hip", ("-fno-slp-vectorize",), BUDGET_STAGE), ("dcn_generic.hip", (), BUDGET_GENERIC),
                                ("codenet_frozen.hip", (), BUDGET_FROZEN), ("codenet_merge.hip", (), BUDGET_MERGE),
                                ("codenet_loss.hip", (), BUDGET_LOSS), ("codenet_preproc.hip", (), BUDGET_PREPROC),
+                               ("codenet_eval.hip", (), BUDGET_EVAL),
                                ("codenet_heads_train.hip", ("-fno-slp-vectorize",), BUDGET_HEADS_TRAIN),
                                ("codenet_units_train.hip", ("-fno-slp-vectorize",), BUDGET_UNITS_TRAIN),
                                ("codenet_stem_train.hip", ("-fno-slp-vectorize",), BUDGET_STEM_TRAIN),
@@ -167,7 +175,7 @@ def check():
                 problems.append("kernel %s not found" % frag)
             sg_ok = 0 if budget is BUDGET_STAGE else SGPR_SPILLS_OK_X
             for n, r in hits:
-                if r["spill"] or r["scratch"] or r["sgpr_spill"] > sg_ok:
+                if r["spill"] or r["scratch"] > SCRATCH_OK.get(frag, 0) or r["sgpr_spill"] > sg_ok:
                     problems.append("%s spills: %s" % (n, r))
                 if r["vgpr"] > cap:
                     problems.append("%s uses %d VGPRs (budget %d)" % (n, r["vgpr"], cap))
@@ -186,7 +194,7 @@ def check():
 
 if __name__ == "__main__":
     res, problems = check()
-    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN) + list(BUDGET_HEADS_FP32_TRAIN) + list(BUDGET_UNITS_FP32_TRAIN) + list(BUDGET_STEM_FP32_TRAIN):
+    for frag in list(BUDGET) + list(BUDGET_STAGE) + list(BUDGET_GENERIC) + list(BUDGET_FROZEN) + list(BUDGET_MERGE) + list(BUDGET_LOSS) + list(BUDGET_PREPROC) + list(BUDGET_EVAL) + list(BUDGET_HEADS_TRAIN) + list(BUDGET_UNITS_TRAIN) + list(BUDGET_STEM_TRAIN) + list(BUDGET_BN_TRAIN) + list(BUDGET_HEADS_FP32_TRAIN) + list(BUDGET_UNITS_FP32_TRAIN) + list(BUDGET_STEM_FP32_TRAIN):
         for n, r in res.items():
             if frag in n:
                 print("%-70s %s" % (n[18:88], r))

@@ -18,6 +18,11 @@ cv2 is not available here: images are read with PIL and the affine crop is done 
     python tools/eval_voc.py --data /data --load_model exp/ctdet/pascal_shufflenetv2_config_c/model_last.pth \
         --res 512 --quantize [--w2] [--maxpool] [--flip_test] [--test_scales 0.5,0.75,1,1.25,1.5] [--nms] [--gpu_pre]
 
+--gpu_eval: the merged detections of every image stay on the device (evalio.DeviceResults.append on the merge block, no
+per-image copy to the host) and one call at the end scores all 20 classes there (evalio.voc_eval_device,
+codenet_eval.hip).  --check_eval: the Python scorer below runs beside it on host copies of the
+same blocks, and any difference in a curve or an AP is an error.
+
 --gpu_pre: the image BYTES go to the device and codenet_amd.preproc (codenet_preproc.hip) builds every test scale and
 mirror there, as the first node of the captured graph -- an integer resize + crop of this project's own (DESIGN.md
 section 7.4b), within 10 grey levels of the float path above on noise, not a copy of cv2's bits either.
@@ -142,6 +147,27 @@ def run_voc(args):
     model = model.cuda().eval().enable_fused()
     results = {}
     ids = sorted(images)[: args.limit or None]
+    gpu_eval, check_eval = bool(getattr(args, "gpu_eval", False)), bool(getattr(args, "check_eval", False))
+    if check_eval and not gpu_eval:
+        raise SystemExit("--check_eval checks the device scorer: it needs --gpu_eval")
+    dev_results = evalio.DeviceResults(len(ids), 20, cap=100, device="cuda") if gpu_eval else None
+    host_too = check_eval or not gpu_eval          # the per-image host copy: only without --gpu_eval, or to check it
+
+    def keep_single(n, img_id, dets, meta):
+        """one scale, no --nms: post_process + the max_per_image cut -- on the host, or (--gpu_eval) by the merge kernel
+        with one scale and without soft-NMS, whose block goes straight into the device table"""
+        if gpu_eval:
+            dev_results.append(harness.merge_scales_native(dets.view(1, 1, -1, 6), [meta], [1.0], 20, nms=False, raw=True), n)
+        if host_too:
+            results[img_id] = evalio.merge_outputs([evalio.post_process(dets.clone(), meta, 20)], 20)
+
+    def keep_multi(n, img_id, replay):
+        if host_too:
+            results[img_id] = replay()[2]
+        else:
+            replay.graph.replay()
+        if gpu_eval:
+            dev_results.append(replay.raw, n)
     static, replay = None, None        # the network + [flip merge +] decode as ONE HIP graph over a static input buffer
     scales = [float(v) for v in str(getattr(args, "test_scales", "1")).split(",")]
     multi = len(scales) > 1 or bool(getattr(args, "nms", False))   # all scales of an image in one graph, merged on the GPU
@@ -169,10 +195,9 @@ def run_voc(args):
                         b.copy_(saved)
             if multi:
                 replay.meta.copy_(harness.scale_metas(metas, scales), non_blocking=True)
-                results[img_id] = replay()[2]
+                keep_multi(n, img_id, replay)
             else:
-                dets = replay()[1].clone()
-                results[img_id] = evalio.merge_outputs([evalio.post_process(dets, metas[0], 20)], 20)
+                keep_single(n, img_id, replay()[1], metas[0])
             if n % 500 == 0:
                 print("%d / %d images" % (n, len(ids)), file=sys.stderr)
             continue
@@ -192,7 +217,7 @@ def run_voc(args):
                         b.copy_(saved)
             static.copy_(inp, non_blocking=True)
             replay.meta.copy_(harness.scale_metas(metas, scales), non_blocking=True)
-            results[img_id] = replay()[2]
+            keep_multi(n, img_id, replay)
             if n % 500 == 0:
                 print("%d / %d images" % (n, len(ids)), file=sys.stderr)
             continue
@@ -209,23 +234,42 @@ def run_voc(args):
                 for b, saved in ranges:
                     b.copy_(saved)
         static.copy_(inp, non_blocking=True)
-        _, dets = replay()
-        dets = dets.clone()
-        per_class = evalio.post_process(dets, meta, 20)
-        results[img_id] = evalio.merge_outputs([per_class], 20)
+        keep_single(n, img_id, replay()[1], meta)
         if n % 500 == 0:
             print("%d / %d images" % (n, len(ids)), file=sys.stderr)
     os.makedirs(args.out, exist_ok=True)
+    scored = None
+    if gpu_eval:
+        gt_dev = evalio.GroundTruth.from_coco_dict(ann, image_ids=ids, valid_ids=list(range(1, 21)), voc=True, device="cuda")
+        scored = evalio.voc_eval_device(dev_results, gt_dev, curves=check_eval)
+        if not host_too:                           # results.json from ONE copy of the table
+            table, count = dev_results.det.cpu().numpy(), dev_results.count.cpu().numpy()
+            for n, img_id in enumerate(ids):
+                rows = table[n, :count[n]]
+                results[img_id] = {c: rows[rows[:, 5] == c - 1, :5].astype(np.float32) for c in range(1, 21)}
     evalio.save_results(results, ids, 20, args.out)
     aps = []
     for c in range(1, 21):
-        rows = [(img_id, float(r[4]), *map(float, r[:4])) for img_id in ids for r in results[img_id][c]]
-        aps.append(voc_eval(rows, gts[c]))
+        if gpu_eval and not check_eval:
+            aps.append(float(scored["ap_07"][c - 1]))
+        else:
+            rows = [(img_id, float(r[4]), *map(float, r[:4])) for img_id in ids for r in results[img_id][c]]
+            rec, prec = voc_eval_curve(rows, gts[c])
+            aps.append(voc_ap07(rec, prec))
+            if gpu_eval:
+                same = (np.array_equal(rec, scored["rec"][c - 1]) and np.array_equal(prec, scored["prec"][c - 1])
+                        and aps[-1] == scored["ap_07"][c - 1] and voc_ap_area(rec, prec) == scored["ap_area"][c - 1])
+                if not same:
+                    raise SystemExit("--check_eval: the device scorer and the Python scorer differ for %s (AP %r vs %r)"
+                                     % (CLASSES[c - 1], float(scored["ap_07"][c - 1]), aps[-1]))
         print("AP for %s = %.4f" % (CLASSES[c - 1], aps[-1]))
     out = {"AP50": float(np.mean(aps)), "per_class": dict(zip(CLASSES, map(float, aps))), "images": len(ids),
            "note": "VOC07 11-point, IoU 0.5; pre-processing by PIL + " + (
                "the integer resize / crop of codenet_preproc.hip on the GPU (--gpu_pre; cv2 absent)" if pre is not None
                else "torch bilinear grid_sample (cv2 absent)")}
+    if gpu_eval:
+        out["scorer"] = "device (evalio.voc_eval_device)" + (", equal to the Python scorer in every curve and AP"
+                                                             if check_eval else "")
     if args.reference_ap50 is not None:
         out["delta_vs_reference"] = out["AP50"] - args.reference_ap50
     print(json.dumps(out))
@@ -282,6 +326,10 @@ def main():
                     "of one pass per scale (faster; QuantAct ranges then update once per image, not once per scale)")
     ap.add_argument("--gpu_pre", action="store_true", help="pre-process on the GPU inside the captured graph "
                     "(codenet_amd.preproc: integer resize + crop, DESIGN.md section 7.4b) instead of on the host")
+    ap.add_argument("--gpu_eval", action="store_true", help="keep the merged detections on the device and score them "
+                    "there (evalio.DeviceResults / voc_eval_device, DESIGN.md section 7.4e): no per-image copy to the host")
+    ap.add_argument("--check_eval", action="store_true", help="with --gpu_eval: also run the Python scorer on host copies "
+                    "and fail on any difference")
     ap.add_argument("--limit", type=int, default=0)
     ap.add_argument("--out", default="gpurun_out/voc_eval")
     ap.add_argument("--proxy-images", type=int, default=0, help="without data / checkpoint: also run the detection-"
